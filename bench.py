@@ -10,6 +10,7 @@ rank r owns the contiguous shard spectral_amd.dist.shard_bounds gives it).  The 
 family of round 1 is timed beside it as a second figure.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs out/   # + the last step's results as out/*.npy
   python bench.py --gpus 8                      # spawns the 8 ranks itself (torch.distributed.run, RCCL) ...
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W   # ... or runs as one of them
@@ -42,6 +43,10 @@ SOLVE_FORMS = {0: "btrapz::ipm_solve_kernel", 1: "btrapz::ipm_solve_split_kernel
                11: "btrapz::ipm_solve_lean_capped_kernel + btrapz::ipm_solve_lean_resume_kernel (two wavefronts per SIMD; one solve = two launches: "
                    "every candidate stops when left alone in its wavefront after 6 iterations, the second launch carries those on; + 3 bucketing "
                    "launches of 5-11 us)"}
+# --dump-outputs: at most this many bytes in all; a batch whose outputs do not fit is dumped as a fixed sample of its
+# candidates, drawn with this seed (the same rows for every array and every run with the same arguments)
+DUMP_BYTES = 64 * 10 ** 6
+DUMP_SEED = 0x5EC7D0
 
 
 def parse():
@@ -75,7 +80,39 @@ def parse():
                          "RCCL resolved by dlopen, else peer copies; no torch in the process).  The launcher starts the second as a fresh "
                          "child when the ranks end non-zero without a line")
     ap.add_argument("--fallback-from", default="", help=argparse.SUPPRESS)   # (set by the launcher: why the ranks did not produce the line)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy in float64, at most 64 MB "
+                         "in all: status and iterations of the candidates rows.npy names (all of them, or a fixed seeded sample of a "
+                         "larger batch), cost and control points of those of them that were solved (solved_rows.npy), and the winner")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+def dump_outputs(d, ctrl, cost, status, iters, index_base, win_idx, win_cost, win_ctrl):
+    """--dump-outputs: the step's results as d/<name>.npy, float64.  rows: the global indices of the candidates dumped --
+    all of this process's batch when everything fits in DUMP_BYTES, else the same seeded sample of it every time; status,
+    iters: of those rows; solved_rows, cost, ctrl: of the rows with status 1 or 2 only, since the other candidates have no
+    solution (cost +inf, include/btrapz_hip.h); winner_index (-1 when no candidate was solved) and, when there is a
+    winner, winner_cost and winner_ctrl."""
+    B, n_ctrl = ctrl.shape
+    win_idx = int(win_idx)
+    whole = {"winner_index": np.array([win_idx])}
+    if win_idx >= 0:
+        whole.update(winner_cost=np.array([win_cost]), winner_ctrl=np.asarray(win_ctrl).reshape(-1))
+    header = 256                                             # .npy header bytes, an upper bound per file
+    row_bytes = 8 * (5 + n_ctrl)      # rows, status, iters + (when solved) solved_rows, cost, ctrl
+    room = DUMP_BYTES - 8 * sum(v.size for v in whole.values()) - header * (6 + len(whole))
+    k = min(B, room // row_bytes)
+    rows = np.arange(B) if k == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+    solved = rows[(status[rows] == 1) | (status[rows] == 2)]
+    out = {"rows": rows + index_base, "status": status[rows], "iters": iters[rows],
+           "solved_rows": solved + index_base, "cost": cost[solved], "ctrl": ctrl[solved]}
+    out.update(whole)
+    os.makedirs(d, exist_ok=True)
+    for n, v in out.items():
+        np.save(os.path.join(d, n + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def self_launch(a):
@@ -290,6 +327,8 @@ def one_process_main(a):
     kernel_ms = float(np.mean([ev.elapsed_ms(e0, e1) for e0, e1 in pairs]))
     win_idx, win_cost, win_ctrl = m.result()
     res = m.download()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res["ctrl"], res["cost"], res["status"], res["iters"], 0, win_idx, win_cost, win_ctrl)
     status, iters = res["status"], res["iters"]
     ok = (status == 1) | (status == 2)
     mean_iters = float(np.mean(iters + 1))
@@ -459,6 +498,9 @@ def main():
     solve_form = solver.ctx.last_solve_form()
 
     status = o["status"].cpu().numpy(); iters = o["iters"].cpu().numpy()
+    if a.dump_outputs and rank == 0:        # (now: the solves below reuse o's buffers)
+        dump_outputs(a.dump_outputs, o["ctrl"].cpu().numpy(), o["cost"].cpu().numpy(), status, iters, index_base,
+                     win_idx.item(), win_cost.item(), wctrl[0].cpu().numpy())
     solved = float(np.mean((status == 1) | (status == 2)))
     it1 = iters + 1                                         # iters holds the index of the last iteration
     mean_iters = float(np.mean(it1))

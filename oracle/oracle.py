@@ -162,27 +162,52 @@ def _bind_mt(L):
 _fast = None
 
 
+def _fast_path():
+    """oracle/libbtrapz_oracle_fast_<CPU model>.so: one file per CPU model, so that a library built on one host is not
+    run on another host's CPU."""
+    import hashlib
+    model = ""
+    try:
+        for line in open("/proc/cpuinfo"):
+            if line.startswith(("model name", "flags")):
+                model += line
+                if line.startswith("flags"):
+                    break
+    except OSError:
+        pass
+    return os.path.join(_HERE, "libbtrapz_oracle_fast_%s.so" % hashlib.sha256(model.encode()).hexdigest()[:10])
+
+
+def _fast_current(path):
+    return os.path.exists(path) and os.path.getmtime(path) >= os.path.getmtime(os.path.join(_HERE, "btrapz_oracle.c"))
+
+
+def build_fast():
+    """The same source at -O3 -march=native for the CPU this runs on (bench.py's cpu_baseline leg only), in oracle/.
+    build() of the repository calls it, so that a built tree holds the library for its host and a benchmark compiles
+    nothing.  Returns the path, or None when oracle/ is not writable and holds no current build for this CPU."""
+    path = _fast_path()
+    if not _fast_current(path):
+        if not os.access(_HERE, os.W_OK):
+            return None
+        subprocess.check_call(["make", "-C", _HERE, "fast", "FAST=" + os.path.basename(path)], stdout=subprocess.DEVNULL)
+    return path
+
+
 def fast_lib():
-    """The same source at -O3 -march=native for the CPU this runs on (bench.py's cpu_baseline leg only).  Built on
-    first use, one file per CPU model so that a library built in the container is not run on the GPU box's host."""
+    """build_fast()'s library, loaded.  A tree that has none for this CPU and cannot be written to (another user's
+    checkout, another host's build) gets one compiled into a private temporary directory, removed once it is loaded."""
     global _fast
     if _fast is None:
-        import hashlib
-        model = ""
-        try:
-            for line in open("/proc/cpuinfo"):
-                if line.startswith(("model name", "flags")):
-                    model += line
-                    if line.startswith("flags"):
-                        break
-        except OSError:
-            pass
-        name = "libbtrapz_oracle_fast_%s.so" % hashlib.sha256(model.encode()).hexdigest()[:10]
-        path = os.path.join(_HERE, name)
-        src = os.path.join(_HERE, "btrapz_oracle.c")
-        if not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src):
-            subprocess.check_call(["make", "-C", _HERE, "fast", "FAST=" + name], stdout=subprocess.DEVNULL)
-        L = C.CDLL(path)
+        path = build_fast()
+        if path is not None:
+            L = C.CDLL(path)
+        else:
+            import tempfile
+            with tempfile.TemporaryDirectory(prefix="btrapz_oracle_fast_") as d:
+                path = os.path.join(d, os.path.basename(_fast_path()))
+                subprocess.check_call(["make", "-C", _HERE, "fast", "FAST=" + path], stdout=subprocess.DEVNULL)
+                L = C.CDLL(path)
         _bind_mt(L)
         _fast = L
     return _fast

@@ -216,8 +216,12 @@ def test_launcher_starts_the_one_process_host_when_the_ranks_end_without_a_line(
     err = p.stderr
     first = err.index("the 2 ranks ended with exit code")
     assert "running the step with --host one-process" in err[first:]
-    assert err.count("bench.py needs a HIP device: the hot path has no CPU fallback") == 3     # two ranks, then the one process
-    assert err.rindex("needs a HIP device") > first                                            # ... the last one AFTER the hand-over
+    refusal = "bench.py needs a HIP device: the hot path has no CPU fallback"
+    # each of the two ranks refused, or had not got that far when the other's refusal made torch.distributed.run end it
+    # with SIGTERM (a rank can also refuse and then be ended while it exits); the rank that ended the launch refused
+    refused, ended = err[:first].count(refusal), err[:first].count("Signal 15 (SIGTERM) received by PID")
+    assert 1 <= refused <= 2 and ended <= 1 and refused + ended >= 2, err
+    assert err[first:].count(refusal) == 1                                                     # then the one process, AFTER the hand-over
 
 
 def test_one_process_argv_drops_what_belongs_to_the_ranks(monkeypatch):
