@@ -501,6 +501,29 @@ int btrapz_solve_warm_device(btrapz_ctx *ctx, const btrapz_shared *shared, const
                              const double *dl_bounds, double *ctrl, double *cost, int *status,
                              int *iters, void *stream);
 
+/* ---- a parameter set per candidate ---------------------------------------------------------------------------------
+ * The entry points above take ONE btrapz_shared for the whole batch.  Here every candidate names its set: sets[n_sets]
+ * (HOST array) holds the ten weights, ds_ref / dl_ref and the acceleration and jerk limits per set, set_index[b] (DEVICE
+ * array) the set of candidate b.  One launch solves the whole batch -- e.g. 128 agents of different target speeds and
+ * limits with 512 candidates each (BASELINE config 5), or the rows of a weight sweep side by side.  Each candidate's result
+ * is, bit for bit, what a uniform batch with its set's btrapz_shared gives it in the same form (btrapz_options.lean pinned).
+ *   variant and delta must be the same in every set (BTRAPZ_EINVAL otherwise).
+ *   set_index[b] outside [0, n_sets): candidate b is not solved -- status BTRAPZ_NO_CORRIDOR, cost +inf, its control
+ *     points untouched -- the other candidates are unaffected (a way to pad a batch).
+ *   seg_count NULL: uniform batch of seg_stride <= BTRAPZ_MAX_SEGMENTS_LONG segments (65..256: the long form, cold only);
+ *     else ragged as btrapz_solve_ragged_device (a cold solve takes its candidates of 65..256 segments through the long
+ *     form, one synchronisation; a warm one gives them BTRAPZ_NO_CORRIDOR, as btrapz_solve_warm_device does).
+ *   warm (may be NULL): as btrapz_solve_warm_device; warm->hint is IGNORED (the candidates are bucketed by set already).
+ *   options: lean and split as elsewhere (0 automatic, 1 where the form applies, -1 never); elastic != 0, cap_iter > 0 and
+ *     compact = 1 are refused with BTRAPZ_EINVAL, automatic cap_iter / compact (0) mean "never" here, as does -1.
+ * The sets' device view and M'QM tables are kept by the context and rebuilt (stream-ordered, through a pinned staging
+ * buffer) only when the sets change: a loop that passes the same sets at every step copies nothing.  Asynchronous. */
+#define BTRAPZ_MAX_SETS 1024
+int btrapz_solve_sets_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_sets, const int *set_index,
+                             const btrapz_options *opt, const btrapz_warm *warm, int B, int seg_stride, const double *seg,
+                             const int *seg_count, const double *init, const double *ref_end, const double *dl_bounds,
+                             double *ctrl, double *cost, int *status, int *iters, void *stream);
+
 /* State (p, v, a) of solved candidates at arbitrary times: x[b][axis][j] at times[b][j] seconds from the
  * start of candidate b's horizon (Bezier evaluation of solve_3d.cc:1366-1388; beyond the last segment the
  * end state is extrapolated at constant velocity).  With times = shift + the cumulative durations of the

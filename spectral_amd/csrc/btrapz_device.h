@@ -142,6 +142,17 @@ __global__ void ipm_solve_lean_capped_ordered_kernel(const KernelArgs a, const d
 __global__ void ipm_solve_lean_resume_kernel(const KernelArgs a, const double *__restrict__ mqm);
 __global__ void ipm_solve_lean_warm_kernel(const KernelArgs a, const double *__restrict__ mqm);
 __global__ void ipm_solve_lean_warm_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm);
+// btrapz_solve_sets_device (btrapz_sets.hip, btrapz_kernels.hip): mqm = the per-set tables [n_sets][168]
+__global__ void ipm_solve_sets_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, int n_keys);
+__global__ void ipm_solve_sets_warm_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, int n_keys);
+__global__ void ipm_solve_lean_sets_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, int n_keys);
+__global__ void ipm_solve_lean_sets_warm_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, int n_keys);
+__global__ void ipm_solve_sets_split_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, const int *set_index, int n_sets);
+__global__ void ipm_solve_long_sets_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, const int *set_index, int n_sets);
+__global__ void sets_hist_kernel(int B, int seg_stride, const int *seg_count, const int *set_index, int n_sets, int n_keys, int *meta);
+__global__ void sets_prefix_kernel(int n_keys, int fixed_S, int *meta);
+__global__ void sets_scatter_kernel(int B, int seg_stride, const int *seg_count, const int *set_index, int n_sets, int n_keys,
+                                    int *meta, int *order, double *axis_obj, int *axis_status, int *axis_iters);
 #define BTRAPZ_SUSPENDED (-7)   // internal: an axis problem the capped launch handed over (never leaves the library)
 __global__ void ipm_solve_long_kernel(const KernelArgs a, const double *__restrict__ mqm);          // 65..256 segments: one axis problem per workgroup
 __global__ void ipm_solve_long_elastic_kernel(const KernelArgs a, const double *__restrict__ mqm);  // rescue pass of the long form (<= 192 segments)
@@ -149,6 +160,7 @@ __global__ void rescue_keys_kernel(int B, int S, const int *seg_count, const int
 __global__ void rescue_init_kernel(int B, int S, const int *seg_count, double *axis_obj, int *axis_status, int *axis_iters);
 struct MqmWeights { double w[2][4]; };   // [axis][ref, dref, acc, jerk]
 __global__ void mqm_table_kernel(MqmWeights w, double *out);
+__global__ void mqm_sets_kernel(const Shared *sets, double *out);   // one block per set: out [n_sets][2][4][21]
 __global__ void rescue_violations_kernel(int B, const double *axis_viol, double *viol);
 __global__ void finalize_kernel(int B, const double *axis_obj, const int *axis_status, const int *axis_iters,
                                 double *cost, int *status, int *iters);

@@ -146,6 +146,13 @@ struct btrapz_ctx {
   int resident_waves = 1024;        // wavefronts the device holds at one per SIMD
   int last_form = -1;               // btrapz_last_solve_form
   int *d_istage = nullptr; size_t istage_cap = 0;
+  // btrapz_solve_sets_device: the device view of every set and its M'QM table, cached by content (h_sets: what the tables
+  // were built from); uploads go through two pinned staging buffers used in turn, the copy out of each marked by its event
+  Shared *d_sets = nullptr; double *d_mqm_sets = nullptr; size_t sets_cap = 0;
+  std::vector<Shared> h_sets;
+  Shared *h_sets_stage[2] = {nullptr, nullptr}; hipEvent_t sets_copied[2] = {nullptr, nullptr};
+  bool sets_copy_pending[2] = {false, false}; int sets_stage_next = 0;
+  int *d_sets_meta = nullptr; size_t sets_meta_cap = 0;   // bucket tables of a sets batch: [n_keys + 1] x 2 + [n_keys]
 };
 
 #define HIPCHK(ctx, call)                                                                     \
@@ -200,6 +207,12 @@ BTRAPZ_EXPORT int btrapz_destroy(btrapz_ctx *c) {
   (void)hipFree(c->d_queue); (void)hipFree(c->d_single_warm); (void)hipFree(c->d_susp_state); (void)hipFree(c->d_susp_ints);
   (void)hipFree(c->d_order); (void)hipFree(c->d_meta); (void)hipFree(c->d_retry); (void)hipFree(c->d_strips); (void)hipFree(c->d_corr_ws); (void)hipFree(c->d_long_list);
   (void)hipFree(c->d_rescue); (void)hipFree(c->d_rescue_meta); (void)hipFree(c->d_argmin_cost); (void)hipFree(c->d_argmin_idx);
+  (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets); (void)hipFree(c->d_sets_meta);
+  for (int i = 0; i < 2; i++) {
+    if (c->sets_copy_pending[i]) (void)hipEventSynchronize(c->sets_copied[i]);
+    if (c->h_sets_stage[i]) (void)hipHostFree(c->h_sets_stage[i]);
+    if (c->sets_copied[i]) (void)hipEventDestroy(c->sets_copied[i]);
+  }
   if (c->ws_free) (void)hipEventDestroy(c->ws_free);
   delete c;
   return BTRAPZ_OK;
@@ -219,6 +232,7 @@ BTRAPZ_EXPORT long long btrapz_workspace_bytes(const btrapz_ctx *c) {
   n += c->stage_cap * sizeof(double) + c->istage_cap * sizeof(int);
   n += (c->d_single ? sizeof(double) * 12 * BTRAPZ_MAX_SEGMENTS : 0) + (c->d_single_warm ? sizeof(double) * 2 * (2 * 64 * 3 + 2 * 36 * 64) : 0);
   n += c->susp_state_doubles * sizeof(double) + c->susp_ints * sizeof(int);
+  n += c->sets_cap * (sizeof(Shared) + sizeof(double) * 168) + c->sets_meta_cap * sizeof(int);   // btrapz_solve_sets_device
   return (long long)n;
 }
 BTRAPZ_EXPORT int btrapz_last_solve_form(const btrapz_ctx *c) { return c ? c->last_form : -1; }
@@ -773,6 +787,199 @@ BTRAPZ_EXPORT int btrapz_solve_warm_device(btrapz_ctx *c, const btrapz_shared *s
                                         void *stream) {
   return solve_common(c, sh, opt, warm, B, seg_stride, seg_count, seg, init, ref_end, dl_bounds, ctrl, cost, status,
                       iters, stream);
+}
+
+// A parameter set per candidate (btrapz_solve_sets_device).  The sets' device view and M'QM tables live in the context,
+// cached by content: a loop that passes the same sets every step copies and builds nothing.  The candidates are bucketed
+// on the device by (set, segment count) -- btrapz_sets.hip -- and solved in ONE launch of an ordered instantiation whose
+// wavefronts each hold one set (ipm_solve_*sets*_kernel).  The split form (few candidates) and the long form (65..256
+// segments; the long candidates of a cold ragged batch) hold one candidate per wavefront / workgroup and read its set
+// themselves.  The forms are chosen as solve_common chooses them; the rescue pass, the two-launch solve and the pre-pass
+// are not served here.
+BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                        const btrapz_options *opt, const btrapz_warm *warm, int B, int seg_stride,
+                                        const double *seg, const int *seg_count, const double *init, const double *ref_end,
+                                        const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters,
+                                        void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  const int S = seg_stride;
+  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS || !set_index || B < 1 || S < 1 || !seg || !init || !ref_end ||
+      !dl_bounds || !ctrl || !cost || !status) {
+    c->err = "invalid argument (sets: 1 <= n_sets <= BTRAPZ_MAX_SETS, set_index and the batch arrays non-null, B >= 1)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!options_ok(c, opt)) return BTRAPZ_EINVAL;
+  if (!seg_count && S > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: uniform batches of at most BTRAPZ_MAX_SEGMENTS_LONG segments";
+    return BTRAPZ_EINVAL;
+  }
+  const bool warm_args = warm && (warm->x0 || warm->lam0 || warm->lam_out);
+  const bool long_form = !seg_count && S > BTRAPZ_MAX_SEGMENTS;
+  if (long_form && warm_args) {
+    c->err = "more than 64 segments: uniform cold solve only";
+    return BTRAPZ_EINVAL;
+  }
+  for (int g = 1; g < n_sets; g++)
+    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
+      c->err = "invalid argument: every parameter set must have the same variant and delta";
+      return BTRAPZ_EINVAL;
+    }
+  if (opt && (opt->elastic != 0 || opt->cap_iter > 0 || opt->compact > 0 || opt->queue > 0 || opt->start != 0)) {
+    c->err = "invalid argument: with parameter sets, elastic, cap_iter > 0, compact = 1, queue and start are not served";
+    return BTRAPZ_EINVAL;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  int rc = ensure_axis_ws(c, 2 * (size_t)B);
+  if (rc != BTRAPZ_OK) return rc;
+  // the sets as the kernels read them (fill_parameters' limits), padding zeroed so that the cache can compare bytes
+  std::vector<Shared> h((size_t)n_sets);
+  for (int g = 0; g < n_sets; g++) {
+    KernelArgs t;
+    memset(&t, 0, sizeof(t));
+    fill_parameters(t, &sets[g], opt, nullptr);
+    memcpy(&h[(size_t)g], &t.sh, sizeof(Shared));
+  }
+  if (h.size() != c->h_sets.size() || memcmp(h.data(), c->h_sets.data(), sizeof(Shared) * h.size()) != 0) {
+    c->h_sets.clear();   // (until the new tables are enqueued)
+    if ((size_t)n_sets > c->sets_cap) {
+      for (int i = 0; i < 2; i++) {
+        if (c->sets_copy_pending[i]) { HIPCHK(c, hipEventSynchronize(c->sets_copied[i])); c->sets_copy_pending[i] = false; }
+        (void)hipHostFree(c->h_sets_stage[i]); c->h_sets_stage[i] = nullptr;
+      }
+      (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets);
+      c->d_sets = nullptr; c->d_mqm_sets = nullptr; c->sets_cap = 0;
+      const size_t cap = (size_t)BTRAPZ_MAX_SETS < 64 * (((size_t)n_sets + 63) / 64) ? (size_t)BTRAPZ_MAX_SETS : 64 * (((size_t)n_sets + 63) / 64);
+      HIPCHK(c, hipMalloc(&c->d_sets, sizeof(Shared) * cap));
+      HIPCHK(c, hipMalloc(&c->d_mqm_sets, sizeof(double) * 168 * cap));
+      for (int i = 0; i < 2; i++) HIPCHK(c, hipHostMalloc((void **)&c->h_sets_stage[i], sizeof(Shared) * cap, hipHostMallocDefault));
+      c->sets_cap = cap;
+    }
+    // Two staging buffers in turn: a buffer is rewritten once ITS copy -- that of the change before the previous one -- has
+    // left it.  The copy itself is stream-ordered behind the launches that still read the device tables (same stream, or
+    // the ws_free event above), so a loop whose sets change at every step waits for the device only when it is two
+    // changes ahead of it.
+    const int si = c->sets_stage_next;
+    c->sets_stage_next = 1 - si;
+    if (!c->sets_copied[si]) HIPCHK(c, hipEventCreateWithFlags(&c->sets_copied[si], hipEventDisableTiming));
+    if (c->sets_copy_pending[si]) HIPCHK(c, hipEventSynchronize(c->sets_copied[si]));
+    memcpy(c->h_sets_stage[si], h.data(), sizeof(Shared) * h.size());
+    HIPCHK(c, hipMemcpyAsync(c->d_sets, c->h_sets_stage[si], sizeof(Shared) * h.size(), hipMemcpyHostToDevice, stream));
+    HIPCHK(c, hipEventRecord(c->sets_copied[si], stream));
+    c->sets_copy_pending[si] = true;
+    hipLaunchKernelGGL(mqm_sets_kernel, dim3((unsigned)n_sets), dim3(192), 0, stream, (const Shared *)c->d_sets, c->d_mqm_sets);
+    HIPCHK(c, hipGetLastError());
+    c->h_sets.swap(h);
+  }
+  KernelArgs a;
+  fill_parameters(a, &sets[0], opt, warm);   // (a.sh is not read: every wavefront reads its own set)
+  a.B = B; a.S = S; a.seg_stride = S;
+  a.order = nullptr; a.seg_count = nullptr; a.cand_prefix = nullptr; a.wave_prefix = nullptr;
+  a.seg = seg; a.init = init; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.mqm = c->d_mqm_sets;
+  a.ctrl = ctrl; a.axis_obj = c->d_axis_obj; a.axis_status = c->d_axis_status; a.axis_iters = c->d_axis_iters;
+  a.axis_viol = c->d_axis_viol; c->viol_valid = 0;
+  a.x_out = nullptr; a.queue = c->d_queue;
+  const bool warm_kernel = a.x0 || a.lam0 || a.lam_out;
+  const double *mq = c->d_mqm_sets;
+  const Shared *dsets = c->d_sets;
+  // the form, as solve_common chooses it for one launch: the split form while 2 B wavefronts fit the device's SIMDs at once
+  // (uniform cold batches of at most 21 segments), two wavefronts per SIMD for batches of >= 1.25 wavefronts per SIMD
+  const int split_opt = opt ? opt->split : 0;
+  const bool split_on = !seg_count && !warm_kernel && S <= 21 &&
+                        (split_opt > 0 || (split_opt == 0 && 2u * (unsigned)B <= (unsigned)c->resident_waves));
+  if (long_form) {
+    c->last_form = 2;
+    hipLaunchKernelGGL(ipm_solve_long_sets_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, stream, a,
+                       mq, dsets, set_index, n_sets);
+    HIPCHK(c, hipGetLastError());
+  } else if (split_on) {
+    c->last_form = 1;
+    hipLaunchKernelGGL(ipm_solve_sets_split_kernel, dim3(2u * (unsigned)B), dim3(64), 0, stream, a, mq, dsets, set_index, n_sets);
+    HIPCHK(c, hipGetLastError());
+  } else {
+    // bucket the candidates by key: set (uniform) or 64 set + 64 - segment count (ragged)
+    const int n_keys = (seg_count ? 64 : 1) * n_sets;
+    const size_t meta_need = 3 * (size_t)n_keys + 2;
+    if (meta_need > c->sets_meta_cap) {
+      (void)hipFree(c->d_sets_meta); c->d_sets_meta = nullptr; c->sets_meta_cap = 0;
+      HIPCHK(c, hipMalloc(&c->d_sets_meta, sizeof(int) * meta_need));
+      c->sets_meta_cap = meta_need;
+    }
+    if ((size_t)B > c->order_cap) {
+      (void)hipFree(c->d_order); c->d_order = nullptr; c->order_cap = 0;
+      HIPCHK(c, hipMalloc(&c->d_order, sizeof(int) * (size_t)B));
+      c->order_cap = B;
+    }
+    int *meta = c->d_sets_meta;
+    HIPCHK(c, hipMemsetAsync(meta + 2 * ((size_t)n_keys + 1), 0, sizeof(int) * (size_t)n_keys, stream));
+    const unsigned nb = (unsigned)((B + 255) / 256);
+    hipLaunchKernelGGL(sets_hist_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, set_index, n_sets, n_keys, meta);
+    hipLaunchKernelGGL(sets_prefix_kernel, dim3(1), dim3(1024), 0, stream, n_keys, seg_count ? 0 : S, meta);
+    hipLaunchKernelGGL(sets_scatter_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, set_index, n_sets, n_keys, meta,
+                       c->d_order, c->d_axis_obj, c->d_axis_status, c->d_axis_iters);
+    HIPCHK(c, hipGetLastError());
+    a.order = c->d_order; a.seg_count = seg_count; a.cand_prefix = meta; a.wave_prefix = meta + n_keys + 1;
+    a.bucket_S = seg_count ? 0 : S;
+    const int lean_opt = opt ? opt->lean : 0;
+    const unsigned est_waves = 2u * (unsigned)((size_t)B / (size_t)(64 / (S < 64 ? S : 64)) + 1);
+    // (slots for more than 64 segments: the packed form, as solve_common chooses it for such a ragged batch)
+    const bool lean_ok = (S >= 3 || seg_count) && S <= BTRAPZ_MAX_SEGMENTS && a.unc_start == 0;
+    const bool lean_on = lean_ok && (lean_opt > 0 || (lean_opt == 0 && 4u * est_waves >= 5u * (unsigned)c->resident_waves));
+    // Upper bound on the wavefront pairs without a host round trip: a key of n candidates needs ceil(n / gpw) pairs, less
+    // than n / gpw + 1, and at most min(n_keys, B) keys are non-empty.  Ragged batches (gpw >= 1): at most 2 B + 2 pairs
+    // against the ragged path's B + 65 -- the surplus wavefronts find no bucket in their binary search and leave.
+    const int gpw_min = seg_count ? 1 : 64 / S;
+    const unsigned blocks = 2u * (unsigned)((size_t)B / (size_t)gpw_min + (size_t)(n_keys < B ? n_keys : B) + 1);
+    auto kernel = lean_on ? (warm_kernel ? ipm_solve_lean_sets_warm_ordered_kernel : ipm_solve_lean_sets_ordered_kernel)
+                          : (warm_kernel ? ipm_solve_sets_warm_ordered_kernel : ipm_solve_sets_ordered_kernel);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, a, mq, dsets, n_keys);
+    HIPCHK(c, hipGetLastError());
+    c->last_form = lean_on ? 8 : 0;
+  }
+  // Cold ragged batch with slots for more than 64 segments: the candidates that HAVE more than 64 (the bucket kernels marked
+  // them "no usable corridor") are solved by the long form, as solve_common does it -- their counts come to the host, one
+  // launch per count over a list; each workgroup reads its candidate's set (warm starts keep them unsolved, as there).
+  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && !warm_kernel) {
+    std::vector<int> counts((size_t)B);
+    HIPCHK(c, hipMemcpyAsync(counts.data(), seg_count, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    const int smax = S < BTRAPZ_MAX_SEGMENTS_LONG ? S : BTRAPZ_MAX_SEGMENTS_LONG;
+    std::vector<std::vector<int>> by_count((size_t)smax + 1);
+    size_t n_long = 0;
+    for (int b = 0; b < B; b++)
+      if (counts[b] > BTRAPZ_MAX_SEGMENTS && counts[b] <= smax) { by_count[(size_t)counts[b]].push_back(b); ++n_long; }
+    if (n_long) {
+      if (n_long > c->long_list_cap) {
+        (void)hipFree(c->d_long_list); c->d_long_list = nullptr; c->long_list_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_long_list, sizeof(int) * n_long));
+        c->long_list_cap = n_long;
+      }
+      std::vector<int> flat;
+      flat.reserve(n_long);
+      for (const auto &l : by_count) flat.insert(flat.end(), l.begin(), l.end());
+      HIPCHK(c, hipMemcpyAsync(c->d_long_list, flat.data(), sizeof(int) * n_long, hipMemcpyHostToDevice, stream));
+      HIPCHK(c, hipStreamSynchronize(stream));   // (flat goes out of scope)
+      size_t off = 0;
+      for (int s = BTRAPZ_MAX_SEGMENTS + 1; s <= smax; s++) {
+        const size_t n = by_count[(size_t)s].size();
+        if (!n) continue;
+        KernelArgs l = a;
+        l.S = s; l.order = c->d_long_list + off; l.bucket_S = (int)n; l.seg_count = nullptr; l.cand_prefix = nullptr; l.wave_prefix = nullptr;
+        hipLaunchKernelGGL(ipm_solve_long_sets_kernel, dim3(2u * (unsigned)n), dim3(64u * (unsigned)((s + 63) / 64)), 0, stream, l,
+                           mq, dsets, set_index, n_sets);
+        HIPCHK(c, hipGetLastError());
+        off += n;
+      }
+      c->last_form |= 16;
+    }
+  }
+  hipLaunchKernelGGL(finalize_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, c->d_axis_obj, c->d_axis_status,
+                     c->d_axis_iters, cost, status, iters);
+  HIPCHK(c, hipGetLastError());
+  c->ws_stream = stream; c->ws_used = true;
+  HIPCHK(c, hipEventRecord(c->ws_free, stream));
+  return BTRAPZ_OK;
 }
 
 BTRAPZ_EXPORT int btrapz_rescue_violations_device(btrapz_ctx *c, int B, double *viol, void *stream_) {

@@ -78,6 +78,13 @@ __device__ __forceinline__ void opaque6(double (&v)[6]) {
 template <int N, class F> __device__ __forceinline__ void static_for(F &&f) {
   if constexpr (N > 0) { static_for<N - 1>(f); f(std::integral_constant<int, N - 1>{}); }
 }
+// The weights and limits a wavefront solves with: the launch's a.sh, or -- SETS, btrapz_solve_sets_device -- the set the
+// wavefront's candidates share (set wave-uniform), read through the constant address space: scalar loads, like a.sh.
+typedef const Shared __attribute__((address_space(4))) cshared_t;
+template <bool SETS> __device__ __forceinline__ auto shared_of(const KernelArgs &a, const Shared *sets, int set) {
+  if constexpr (SETS) return (cshared_t *)(sets + set);
+  else return &a.sh;
+}
 // Rows kept by a solve.  FULL: all 18 rows of a segment, as the reference assembles them.  Otherwise 15: the first
 // position, velocity and acceleration row of a segment (rows 0, 6, 11) state, about the joint at its start, what the
 // previous segment's last rows (5, 10, 14) state about the same joint from the other side -- t c_{k,5} = t' c_{k+1,0},

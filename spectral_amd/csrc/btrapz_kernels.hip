@@ -83,15 +83,24 @@ namespace btrapz {
 // the rescue pass; ragged batches: by segment count), restores the iterate and carries on: the same iterates, bit for
 // bit, as the one-launch solve.
 enum { SUSP_FIELDS = 3 + 4 * 15 + 3 + 8 };
+// SETS = true (btrapz_solve_sets_device): every candidate names its parameter set, and a wavefront's weights, limits and
+// M'QM table come from sets[set] and mqm + 168 set through scalar loads as those of a one-set batch do.  Ordered cold /
+// warm instantiations: the candidates are bucketed by set (and segment count) so that a wavefront holds ONE set; n_keys:
+// slots of the tables.  Split and long form: one candidate per wavefront / workgroup, its set read from set_index (n_keys
+// = the number of sets; a candidate whose index is outside [0, n_keys) is not solved: BTRAPZ_NO_CORRIDOR).
 template <bool WARM, bool ORDERED, bool ELASTIC = false, bool QUEUE = false, bool SPLIT = false, bool MULTI = false,
-          bool CAPPED = false, bool RESUME = false>
+          bool CAPPED = false, bool RESUME = false, bool SETS = false>
 __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double *__restrict__ mqm, double (*lds)[64],
-                                               const int wave_id, const int lane, double *wgs = nullptr, const int wv = 0) {
+                                               const int wave_id, const int lane, double *wgs = nullptr, const int wv = 0,
+                                               const Shared *sets = nullptr, const int n_keys = 0,
+                                               const int *set_index = nullptr) {
   static_assert(!QUEUE || (!WARM && !ORDERED && !ELASTIC), "the queue serves uniform cold batches");
   static_assert(!SPLIT || (!ORDERED && !ELASTIC && !QUEUE), "the split form serves uniform batches");
   static_assert(!MULTI || (!WARM && !ORDERED && !QUEUE && !SPLIT), "the long form serves uniform cold batches (and their rescue pass) -- and, launched once per segment count with a candidate list in a.order of a.bucket_S entries, the long candidates of a ragged batch");
   static_assert(!(CAPPED || RESUME) || (!WARM && !ELASTIC && !QUEUE && !SPLIT && !MULTI && !(CAPPED && RESUME)), "capped / resume: packed cold form");
   static_assert(!RESUME || ORDERED, "the resume pass reads its problems from per-axis lists");
+  static_assert(!SETS || (!ELASTIC && !QUEUE && !CAPPED && !RESUME && (ORDERED ? !SPLIT && !MULTI : SPLIT || MULTI)),
+                "sets: ordered cold / warm forms, split and long form");
   constexpr bool PERAXIS = ELASTIC || RESUME;   // one candidate list and one set of bucket tables per axis
   // value of the previous / next segment's lane (0 beyond the ends of the wavefront -- or, long form, of the workgroup)
   auto from_prev = [&](double x) -> double {
@@ -122,7 +131,20 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
   // the axis is wave-uniform
   const int axis = __builtin_amdgcn_readfirstlane(wave_id & 1);
   int S, pair = wave_id >> 1, ncand = a.B, cand0 = 0;
-  if constexpr (ORDERED) {
+  [[maybe_unused]] int set = 0;
+  if constexpr (SETS && ORDERED) {
+    // n_keys slots: key = set (uniform batch of a.bucket_S segments) or 64 set + 64 - segment count (ragged)
+    if (pair >= a.wave_prefix[n_keys]) return;
+    int s = 0, hi = n_keys;
+    while (hi - s > 1) {
+      const int mid = (s + hi) >> 1;
+      if (a.wave_prefix[mid] <= pair) s = mid; else hi = mid;
+    }
+    set = a.bucket_S ? s : s >> 6;
+    S = a.bucket_S ? a.bucket_S : 64 - (s & 63);
+    pair -= a.wave_prefix[s]; cand0 = a.cand_prefix[s]; ncand = a.cand_prefix[s + 1] - a.cand_prefix[s];
+    set = __builtin_amdgcn_readfirstlane(set);
+  } else if constexpr (ORDERED) {
     // ragged batch: candidates are bucketed by segment count; find this wave's bucket (wave-uniform)
     // (rescue pass: one set of tables and one candidate list per axis, the stalled axis problems only)
     const int *wave_prefix = a.wave_prefix + (PERAXIS ? axis * 198 : 0), *cand_prefix = a.cand_prefix + (PERAXIS ? axis * 198 : 0);
@@ -139,6 +161,21 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
   } else {
     S = a.S;
   }
+  if constexpr (SETS && !ORDERED) {
+    // split / long form: ONE candidate per wavefront (workgroup), the set is uniform by construction.  (Long form with a
+    // list: the candidates of a ragged batch with a.S > 64 segments, the list's length in a.bucket_S; see below.)
+    const bool listed_ = MULTI && a.order != nullptr;
+    const int n_ = listed_ ? a.bucket_S : a.B;
+    const int p_ = pair < n_ ? pair : n_ - 1;
+    const int b_ = listed_ ? a.order[p_] : p_;
+    set = __builtin_amdgcn_readfirstlane(set_index[b_]);
+    if (set < 0 || set >= n_keys) {   // not solved (every wavefront of the workgroup leaves here: same candidate)
+      if (pair < n_ && lane == 0 && wv == 0) {
+        a.axis_obj[2 * (size_t)b_ + axis] = 0.0; a.axis_status[2 * (size_t)b_ + axis] = BTRAPZ_NO_CORRIDOR; a.axis_iters[2 * (size_t)b_ + axis] = 0;
+      }
+      return;
+    }
+  }
   S = __builtin_amdgcn_readfirstlane(S);
   const int gpw = SPLIT ? 3 : MULTI ? 1 : 64 / S;   // split form: three copies of one problem (3 S <= 64, the host checks)
   const int kk = MULTI ? wv * 64 + lane : lane;     // long form: the workgroup's lanes are the segments
@@ -153,11 +190,11 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
   const int my_step = top ? k : (bot ? S - 1 - k : m);  // the step at which this lane owns a pivot
   const size_t BS = (size_t)a.B * a.seg_stride;
   const double *sg = a.seg;
-  const Shared &sh = a.sh;
+  const auto &sh = *shared_of<SETS>(a, sets, set);
   const int variant = sh.variant;
   // P block (solve_3d.cc:159-171) from the batch-invariant MQM_d = M' pQp_d M: the table is
   // wave-uniform (one axis per wave) -> scalar loads.
-  const double *__restrict__ mq = mqm + axis * 84;
+  const double *__restrict__ mq = mqm + (SETS ? (size_t)set * 168 : 0) + axis * 84;
   const size_t lam_row = (size_t)a.B * a.seg_stride;
   const double eps = a.eps;
   [[maybe_unused]] const double edelta0 = ELASTIC ? a.elastic_delta : 0.0;
@@ -1273,6 +1310,33 @@ __global__ __launch_bounds__(64) void ipm_solve_warm_ordered_kernel(const Kernel
   __shared__ double lds[lds_rows<false>()][64];
   ipm_solve_body<true, true>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x);
 }
+// btrapz_solve_sets_device: a parameter set per candidate (SETS above), candidates bucketed by set (and segment count)
+__global__ __launch_bounds__(64) void ipm_solve_sets_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                    const Shared *sets, int n_keys) {
+  __shared__ double lds[lds_rows<false>()][64];
+  ipm_solve_body<false, true, false, false, false, false, false, false, true>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x,
+                                                                             nullptr, 0, sets, n_keys);
+}
+__global__ __launch_bounds__(64) void ipm_solve_sets_warm_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                         const Shared *sets, int n_keys) {
+  __shared__ double lds[lds_rows<false>()][64];
+  ipm_solve_body<true, true, false, false, false, false, false, false, true>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x,
+                                                                            nullptr, 0, sets, n_keys);
+}
+__global__ __launch_bounds__(64) void ipm_solve_sets_split_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                  const Shared *sets, const int *set_index, int n_sets) {
+  __shared__ double lds[21][64];
+  ipm_solve_body<false, false, false, false, true, false, false, false, true>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x,
+                                                                             nullptr, 0, sets, n_sets, set_index);
+}
+__global__ __launch_bounds__(256) void ipm_solve_long_sets_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                  const Shared *sets, const int *set_index, int n_sets) {
+  __shared__ double lds[4][lds_rows<false>()][64];
+  __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
+  const int wv = (int)threadIdx.x >> 6;
+  ipm_solve_body<false, false, false, false, false, true, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63,
+                                                                             wgs, wv, sets, n_sets, set_index);
+}
 // Uniform cold batches much larger than the machine, two launches (CAPPED / RESUME above): every group stops at
 // cap_iter iterations; the unfinished ones are carried on by the resume launch, like with like, far ones first.
 __global__ __launch_bounds__(64) void ipm_solve_capped_kernel(const KernelArgs a, const double *__restrict__ mqm) {
@@ -1469,6 +1533,32 @@ __global__ void rescue_init_kernel(int B, int S, const int *seg_count, double *a
 // ---- batch-invariant table M' pQp_d M (solve_3d.cc:87-143), built in stream order whenever the weights change --------
 // thread = (axis, derivative d, packed upper-triangle entry): out[axis][d][SYM(i, j)].  pQp_d(a, b) = w_d * prod_{r<d}
 // (a - r)(b - r) / (a + b - 2d + 1) for a, b >= d (:87-113); M = Bernstein -> monomial (:122-127).
+// (one entry, thread id = (axis, d, e), for the per-set tables of btrapz_solve_sets_device: the expressions of
+//  mqm_table_kernel below, evaluated in the same order with contraction off -- a set's table is the bits of the one-set
+//  table of the same weights: tests/test_gpu_param_sets.py compares one-set solves bit for bit)
+__device__ __forceinline__ double mqm_entry(const double (&w)[2][4], const int id) {
+#pragma clang fp contract(off)   // same expressions, same rounding as mqm_table_kernel and btrapz_mqm_table_host
+  const int axis = id / 84, d = (id % 84) / 21, e = id % 21;
+  int j = 0;
+  while ((j + 1) * (j + 2) / 2 <= e) ++j;
+  const int i = e - j * (j + 1) / 2;
+  const double M[6][6] = {{1, 0, 0, 0, 0, 0},      {-5, 5, 0, 0, 0, 0},      {10, -20, 10, 0, 0, 0},
+                          {-10, 30, -30, 10, 0, 0}, {5, -20, 30, -20, 5, 0}, {-1, 5, -10, 10, -5, 1}};
+  const double wd = w[axis][d];
+  double acc = 0.0;
+  for (int a = d; a < 6; a++) {
+    double t = 0.0;   // (M' pQp)(i, b) summed against M(b, j)
+    for (int b = d; b < 6; b++) {
+      double num = wd;
+      for (int r = 0; r < d; r++) num *= (double)((a - r) * (b - r));
+      t += num / (double)(a + b - 2 * d + 1) * M[b][j];
+    }
+    acc += M[a][i] * t;
+  }
+  return acc;
+}
+// (mqm_table_kernel keeps its own copy of the expressions: written as a call of mqm_entry it compiles to other
+//  instructions -- another loop structure and register assignment -- and the one-set path's kernels stay as they were)
 __global__ void mqm_table_kernel(MqmWeights w, double *out) {
 #pragma clang fp contract(off)   // same expressions, same rounding as btrapz_mqm_table_host (find_traj's table)
   const int id = threadIdx.x;
@@ -1491,6 +1581,15 @@ __global__ void mqm_table_kernel(MqmWeights w, double *out) {
     acc += M[a][i] * t;
   }
   out[id] = acc;
+}
+// btrapz_solve_sets_device: one block per set, out[set][2][4][21] from sets[set].w_s / w_l
+__global__ void mqm_sets_kernel(const Shared *sets, double *out) {
+  const int id = threadIdx.x;
+  if (id >= 168) return;
+  const Shared &sh = sets[blockIdx.x];
+  double w[2][4];
+  for (int d = 0; d < 4; d++) { w[0][d] = sh.w_s[d]; w[1][d] = sh.w_l[d]; }
+  out[(size_t)blockIdx.x * 168 + id] = mqm_entry(w, id);
 }
 
 // viol[b][c] = the larger of the two axes' class-c violation (btrapz_rescue_violations_device)

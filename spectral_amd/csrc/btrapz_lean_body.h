@@ -33,12 +33,17 @@ enum { LN_LL = 0, LN_LU = 15, LN_RED = 30, LN_XB = 34, LN_XI = 37, LN_ROWS = 40 
 enum { LEAN_SUSP_FIELDS = 3 + 4 * 15 + 3 + 8 };   // slot stride: SUSP_FIELDS of the packed form (the host sizes one workspace);
                                                   // the lean record itself is 69 doubles per lane (3 + 3 + 60 + 3 of bookkeeping)
 
-template <bool ORDERED, bool CAPPED, bool RESUME, bool WARM = false>
+// SETS (btrapz_solve_sets_device; btrapz_sets.hip): the candidates are bucketed by parameter set (and segment count), a
+// wavefront holds one set, and its weights, limits and M'QM table (mqm + 168 set) are read as a one-set launch reads a.sh
+// and its table: scalar loads through laundered constant-address-space pointers.  n_keys: slots of the bucket tables.
+template <bool ORDERED, bool CAPPED, bool RESUME, bool WARM = false, bool SETS = false>
 __device__ __forceinline__ void lean_solve_body(const KernelArgs &a, const double *__restrict__ mqm, double (*lds)[64],
-                                                const int wave_id, const int lane) {
+                                                const int wave_id, const int lane, const Shared *sets = nullptr,
+                                                const int n_keys = 0) {
   static_assert(!(CAPPED && RESUME), "one launch is the first or the second");
   static_assert(!RESUME || ORDERED, "the resume pass reads its problems from per-axis lists");
   static_assert(!WARM || (!CAPPED && !RESUME), "warm starts: one launch");
+  static_assert(!SETS || (ORDERED && !CAPPED && !RESUME), "sets: the ordered one-launch forms");
   constexpr bool FULL = false;
   constexpr int NR = 15;
   constexpr bool PERAXIS = RESUME;
@@ -52,7 +57,20 @@ __device__ __forceinline__ void lean_solve_body(const KernelArgs &a, const doubl
   constexpr bool SMALL_S = ORDERED;
   const int axis = __builtin_amdgcn_readfirstlane(wave_id & 1);
   int S, pair = wave_id >> 1, ncand = a.B, cand0 = 0;
-  if constexpr (ORDERED) {
+  [[maybe_unused]] int set = 0;
+  if constexpr (SETS) {
+    // n_keys slots: key = set (uniform batch of a.bucket_S segments) or 64 set + 64 - segment count (ragged)
+    if (pair >= a.wave_prefix[n_keys]) return;
+    int s = 0, hi = n_keys;
+    while (hi - s > 1) {
+      const int mid = (s + hi) >> 1;
+      if (a.wave_prefix[mid] <= pair) s = mid; else hi = mid;
+    }
+    set = a.bucket_S ? s : s >> 6;
+    S = a.bucket_S ? a.bucket_S : 64 - (s & 63);
+    pair -= a.wave_prefix[s]; cand0 = a.cand_prefix[s]; ncand = a.cand_prefix[s + 1] - a.cand_prefix[s];
+    set = __builtin_amdgcn_readfirstlane(set);
+  } else if constexpr (ORDERED) {
     const int *wave_prefix = a.wave_prefix + (PERAXIS ? axis * 198 : 0), *cand_prefix = a.cand_prefix + (PERAXIS ? axis * 198 : 0);
     if (pair >= wave_prefix[65]) return;
     int s = 1, hi = 65;
@@ -91,8 +109,9 @@ __device__ __forceinline__ void lean_solve_body(const KernelArgs &a, const doubl
   //    1.5e-6 of this arrangement's) and 48 % SLOWER, 3.97 -> 5.86 ms: an odd joint keeps TWO 3 x 3 blocks (S^-1 C_a,
   //    S^-1 C_b) where a chain joint keeps one -- +18 registers in a kernel that has none: scratch 92 -> 316-412 B per
   //    lane, and no longer read-only data: 112 scratch loads and 21 stores per iteration instead of 15 and 4.
-  const Shared &sh = a.sh;
+  const auto &sh = *shared_of<SETS>(a, sets, set);
   const int variant = sh.variant;
+  [[maybe_unused]] cshared_t *const set_sh = SETS ? (cshared_t *)(sets + set) : nullptr;   // (the row limits, below)
   // The kernel's arguments as the loop and the write-back see them: through a pointer into the kernarg segment that is
   // laundered once per iteration -- scalar loads where the value is used.  Left to itself the optimiser loads every
   // argument at the top of the kernel and carries ~100 SGPRs of them through the loop as spills in VGPR lanes
@@ -104,7 +123,7 @@ __device__ __forceinline__ void lean_solve_body(const KernelArgs &a, const doubl
   // (constant address space: the table is read through scalar loads INSIDE the loop -- the pointer is laundered there, or
   //  the optimiser hoists all 168 dwords of it out of the loop and spills them to VGPR lanes: 180 v_readlane per iteration)
   typedef const double __attribute__((address_space(4))) ctable_t;
-  ctable_t *mq = (ctable_t *)(mqm + axis * 84);
+  ctable_t *mq = (ctable_t *)(mqm + (SETS ? (size_t)set * 168 : 0) + axis * 84);
   const double inv_m = 1.0 / ((double)(2 * NR) * (double)S);
   auto from_prev = [&](double x) -> double { return dpp_prev(x); };
   auto from_next = [&](double x) -> double { return dpp_next(x); };
@@ -142,7 +161,7 @@ __device__ __forceinline__ void lean_solve_body(const KernelArgs &a, const doubl
 #define LUP(r) ((r) < 5 ? phi0 + (double)(r) * dphi : (r) == 5 ? mphi : (r) < 10 ? vh[((r) >= 7 && (r) <= 9) ? (r) - 7 : 0] : (r) == 10 ? mvhi : (r) < 15 ? ahi : jhi)
 // (read where they are used, through the laundered kernarg pointer: four scalars less to carry through the loop)
 #define ROW_LIMITS_ACC()                                                                            \
-  const double __attribute__((address_space(4))) *lim_ = &ka->sh.acc_s[0] + 2 * axis;               \
+  const double __attribute__((address_space(4))) *lim_ = (SETS ? &set_sh->acc_s[0] : &ka->sh.acc_s[0]) + 2 * axis; \
   asm volatile("" : "+s"(lim_));   /* (a copy: some passes run under a divergent condition) */      \
   const double alo = lim_[0] * t, ahi = lim_[1] * t, jlo = lim_[4] * t * t, jhi = lim_[5] * t * t
 #if LEAN_RELOAD
@@ -1068,6 +1087,12 @@ __device__ __forceinline__ void lean_solve_body(const KernelArgs &a, const doubl
   LEAN_KERNEL void name(const KernelArgs a, const double *__restrict__ mqm) {                \
     __shared__ double lds[LN_ROWS][64];                                                      \
     lean_solve_body<__VA_ARGS__>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x);            \
+  }
+// btrapz_solve_sets_device: mqm = the per-set tables [n_sets][168], sets [n_sets]
+#define LEAN_SETS_INSTANCE(name, WARM_)                                                                            \
+  LEAN_KERNEL void name(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, int n_keys) {    \
+    __shared__ double lds[LN_ROWS][64];                                                                           \
+    lean_solve_body<true, false, false, WARM_, true>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x, sets, n_keys); \
   }
 
 }  // namespace btrapz

@@ -121,7 +121,7 @@ EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "bt
            "btrapz_device_count", "btrapz_solve_batch_device", "btrapz_argmin_device",
            "btrapz_sample_device", "btrapz_solve_batch_host", "btrapz_solve_ragged_device",
            "btrapz_corridor_batch_device", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
-           "btrapz_eval_states_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
+           "btrapz_solve_sets_device", "btrapz_eval_states_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
            "btrapz_prism_corridor_batch_device",
            "btrapz_find_traj_last_iterations", "btrapz_argmin_pairs_device", "btrapz_options_init",
            "btrapz_rescue_violations_device", "btrapz_find_traj_last_status", "btrapz_debug_mqm_tables",
@@ -218,6 +218,8 @@ def lib():
                                                   C.c_int, dp, ip, vp]
         l.btrapz_solve_warm_device.argtypes = [vp, C.POINTER(CShared), C.POINTER(COptions), C.POINTER(CWarm), C.c_int,
                                                C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
+        l.btrapz_solve_sets_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.POINTER(COptions), C.POINTER(CWarm),
+                                               C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
         l.btrapz_eval_states_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, vp]
         l.btrapz_prism_bounds_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, ip, vp]
         l.btrapz_prism_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int,
@@ -434,6 +436,24 @@ class Context:
                                                    ptr(seg), ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds),
                                                    ptr(ctrl), ptr(cost), ptr(status), ptr(iters),
                                                    C.c_void_p(stream or 0)), "btrapz_solve_warm_device")
+
+    def solve_sets_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
+                          iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, hint=None, stream=None,
+                          max_iter=0, eps=0.0, elastic=0, cap_iter=0, lean=0, compact=0, split=0):
+        """btrapz_solve_sets_device: sets = list of layout.Shared (one per parameter set), set_index = [B] int32 device
+        tensor (a value outside [0, len(sets)): that candidate is not solved, status NO_CORRIDOR); seg_count None =
+        uniform batch.  Warm start as in solve_warm_device (hint is accepted and ignored by the library)."""
+        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
+        opt = _options(max_iter, eps, elastic, split=split, cap_iter=cap_iter, lean=lean, compact=compact)
+        raw = lambda t: t.data_ptr() if t is not None else None
+        use_warm = any(t is not None for t in (x0, lam0, lam_out, hint))
+        warm = CWarm(raw(x0), raw(lam0), raw(lam_out), float(mu0), float(smin), raw(hint)) if use_warm else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_solve_sets_device(self._h, arr, len(sets), ptr(set_index), C.byref(opt),
+                                                   C.byref(warm) if warm is not None else None, B, seg_stride, ptr(seg),
+                                                   ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
+                                                   ptr(cost), ptr(status), ptr(iters), C.c_void_p(stream or 0)),
+                    "btrapz_solve_sets_device")
 
     def workspace_bytes(self):
         """btrapz_workspace_bytes: device memory the context holds for its launches right now."""

@@ -185,6 +185,44 @@ class BatchSolver:
                                      max_iter=max_iter, eps=eps, elastic=elastic, elastic_tol=elastic_tol, cap_iter=cap_iter, lean=lean, compact=compact)
         return o
 
+    def _sets_call(self, B, S, sets, set_index, rec, seg_count, o, warm, keep_multipliers, options):
+        assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
+        warm = warm or {}
+        x0, lam0 = warm.get("x0"), warm.get("lam")
+        if x0 is not None:
+            assert x0.dtype == torch.float64 and x0.is_contiguous() and tuple(x0.shape) == (B, 2, S, 3)
+        if lam0 is not None:
+            assert lam0.dtype == torch.float64 and lam0.is_contiguous() and tuple(lam0.shape) == (2, 36, B, S)
+        lam_out = None
+        if keep_multipliers:
+            lam_out = lam0 if lam0 is not None else torch.empty((2, 36, B, S), dtype=torch.float64, device=self.device)
+            o = dict(o); o["lam"] = lam_out
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.ctx.solve_sets_device(B, S, sets, set_index, rec.seg if seg_count is None else rec["seg"], seg_count,
+                                   rec.init if seg_count is None else rec["init"],
+                                   rec.ref_end if seg_count is None else rec["ref_end"],
+                                   rec.dl_bounds if seg_count is None else rec["dl_bounds"], o["ctrl"], o["cost"],
+                                   o["status"], o["iters"], x0=x0, lam0=lam0, lam_out=lam_out, mu0=warm.get("mu0", 0.0),
+                                   smin=warm.get("smin", 0.0), hint=warm.get("hint"), stream=stream, **options)
+        return o
+
+    def solve_sets(self, dbatch, sets, set_index, warm=None, keep_multipliers=False, out=None, **options):
+        """A parameter set per candidate (btrapz_solve_sets_device): sets is a list of layout.Shared, set_index an int32
+        device tensor [B] naming each candidate's set (outside [0, len(sets)): not solved, status NO_CORRIDOR, cost
+        +inf).  warm / keep_multipliers as in solve(); options: max_iter, eps, lean (0 / 1 / -1), cap_iter and compact
+        (0 or -1: the sets path runs one launch without the pre-pass).  Returns the dict of device tensors."""
+        o = out if out is not None else self._buffers(dbatch.B, dbatch.S)
+        return self._sets_call(dbatch.B, dbatch.S, sets, set_index, dbatch, None, o, warm, keep_multipliers, options)
+
+    def solve_sets_ragged(self, rec, sets, set_index, warm=None, keep_multipliers=False, **options):
+        """solve_sets for a ragged batch record (from corridor_batch): candidates of up to 64 segments."""
+        d = self.device
+        B, st = rec["B"], rec["seg_stride"]
+        o = dict(ctrl=torch.zeros((B, 12 * st), dtype=torch.float64, device=d),
+                 cost=torch.empty(B, dtype=torch.float64, device=d),
+                 status=torch.empty(B, dtype=torch.int32, device=d), iters=torch.empty(B, dtype=torch.int32, device=d))
+        return self._sets_call(B, st, sets, set_index, rec, rec["seg_count"], o, warm, keep_multipliers, options)
+
     def argmin(self, cost, group=None, index_base=0):
         """Arg-min of cost over contiguous groups (default: the whole batch). Device tensors."""
         B = cost.numel()

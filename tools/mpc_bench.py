@@ -24,6 +24,7 @@ workload generation, not part of the library), btrapz_eval_states_device x2, btr
 btrapz_argmin_device(group = candidates per agent).  One JSON line on stdout.  --dump writes the winners of a few
 agents at --check steps (problem + control points) so that a test can hold them against the oracle."""
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -52,6 +53,8 @@ def main(argv=None):
     ap.add_argument("--mu0", type=float, default=0.0, help="btrapz_warm.mu0 (0 = library default)")
     ap.add_argument("--smin", type=float, default=0.0, help="btrapz_warm.smin (0 = library default)")
     ap.add_argument("--no-hint", action="store_true", help="do not pass the previous iteration counts as scheduling hint")
+    ap.add_argument("--per-agent-params", action="store_true",
+                    help="every agent its own ds_ref and acceleration limits (btrapz_solve_sets_device: one set per agent, one launch)")
     ap.add_argument("--roll", default="cold", choices=["lam", "x0", "cold"],
                     help="what a step that rolls the window starts from: previous plan + rolled multipliers, plan only, nothing")
     ap.add_argument("--trace", action="store_true", help="per-step latency / iterations on stderr")
@@ -117,6 +120,15 @@ def main(argv=None):
         raise SystemExit("rank %d has no agents (%d agents over %d ranks)" % (rank, G_all, world_n))
     solver = BatchSolver(local_rank)
     dev = solver.device
+    agent_sets = set_index = None
+    if a.per_agent_params:
+        # target speed within +-20 % of the header's, longitudinal / lateral acceleration limits within 0.8..1.2 of its:
+        # drawn per agent of the whole fleet from one seed, so that a sharded run gives every agent the same set
+        prng = np.random.default_rng(synth.SEED_BASE + 55)
+        f_ds, f_acc, f_lat = (prng.uniform(0.8, 1.2, size=G_all) for _ in range(3))
+        agent_sets = [dataclasses.replace(sh, ds_ref=sh.ds_ref * f_ds[g], dds=(sh.dds[0] * f_acc[g], sh.dds[1] * f_acc[g]),
+                                          ddl=(sh.ddl[0] * f_lat[g], sh.ddl[1] * f_lat[g])) for g in range(g_lo, g_hi)]
+        set_index = torch.from_numpy(np.repeat(np.arange(G), C).astype(np.int32)).to(dev)
     wseg = torch.from_numpy(world.seg).to(dev)                       # [F][B][pieces]
     dl_bounds = torch.from_numpy(world.dl_bounds).to(dev)
     init = torch.from_numpy(world.init).to(dev).clone()
@@ -167,11 +179,14 @@ def main(argv=None):
                 # difficulty persists: hard / infeasible candidates share wavefronts.  Coarse classes -- everything that
                 # took fewer than 8 iterations is "easy" -- so that easy candidates keep their memory order.
                 warm["hint"] = torch.clamp((prev["iters"] - 4) // 4 + 1, min=1).to(torch.int32)
-        out = solver.solve(db, sh, warm=warm, keep_multipliers=not a.cold,
-                           out=dict(ctrl=torch.empty((B, 12 * S), dtype=torch.float64, device=dev),
-                                    cost=torch.empty(B, dtype=torch.float64, device=dev),
-                                    status=torch.empty(B, dtype=torch.int32, device=dev),
-                                    iters=torch.empty(B, dtype=torch.int32, device=dev)))
+        bufs = dict(ctrl=torch.empty((B, 12 * S), dtype=torch.float64, device=dev),
+                    cost=torch.empty(B, dtype=torch.float64, device=dev),
+                    status=torch.empty(B, dtype=torch.int32, device=dev),
+                    iters=torch.empty(B, dtype=torch.int32, device=dev))
+        if agent_sets is not None:
+            out = solver.solve_sets(db, agent_sets, set_index, warm=warm, keep_multipliers=not a.cold, out=bufs)
+        else:
+            out = solver.solve(db, sh, warm=warm, keep_multipliers=not a.cold, out=bufs)
         bi, bc = solver.argmin(out["cost"], group=C)
         # next initial state of every agent: its winner's state dt later
         nxt = solver.eval_states(db, out["ctrl"], torch.full((B, 1), a.dt, dtype=torch.float64, device=dev))
@@ -200,6 +215,9 @@ def main(argv=None):
                     dumped.append(dict(step=n, agent=g_lo + g, seg=seg[:, wi].cpu().numpy(), init=db.init[wi].cpu().numpy(),
                                        ref_end=ref_end[wi].cpu().numpy(), dl_bounds=world.dl_bounds[wi],
                                        ctrl=out["ctrl"][wi].cpu().numpy()))
+                    if agent_sets is not None:   # the agent's own set: ds_ref, dds, ddl
+                        s_ = agent_sets[g]
+                        dumped[-1].update(ds_ref=np.float64(s_.ds_ref), dds=np.array(s_.dds), ddl=np.array(s_.ddl))
         prev = dict(db=db, ctrl=out["ctrl"], lam=out.get("lam"), j0=j0, iters=out["iters"])
     wall = time.perf_counter() - wall0
     lat = np.array(lat)
@@ -218,7 +236,7 @@ def main(argv=None):
         "solved_fraction_mean": float(np.mean(solved)), "solved_fraction_min": float(np.min(solved)),
         "candidates_per_s": B * 1e3 / float(steady.mean()),
         "dumped_winners": len(dumped),
-        "n_gpus": world_n, "agents_per_gpu": G, "parallelism": "agents sharded over %d GPU(s), per-agent arg-min local, no collective" % world_n,
+        "n_gpus": world_n, "agents_per_gpu": G, "per_agent_params": bool(a.per_agent_params), "parallelism": "agents sharded over %d GPU(s), per-agent arg-min local, no collective" % world_n,
         "last_winners": [int(v) + g_lo * C if v >= 0 else -1 for v in bi.cpu().tolist()],   # global candidate indices, this rank's agents
     }
     if world_n > 1:
