@@ -524,6 +524,55 @@ int btrapz_solve_sets_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_s
                              const int *seg_count, const double *init, const double *ref_end, const double *dl_bounds,
                              double *ctrl, double *cost, int *status, int *iters, void *stream);
 
+/* ---- gradients of a solve (vector-Jacobian product) -----------------------------------------------------------------
+ * For every candidate b of a solve, x = ctrl[b] is the QP's optimum and cost[b] = x'Px/2 + q'x.  Given cotangents
+ * ctrl_bar = dL/dctrl and cost_bar = dL/dcost (either may be NULL: zero), this call returns dL/dtheta for the solve's
+ * inputs theta, by implicit differentiation of the KKT conditions at x with the active set of the solve: with
+ * xbar' = ctrl_bar + cost_bar (P x + q), it solves
+ *     [ P  A' ] [v]   [xbar']
+ *     [ A  0  ] [w] = [  0  ]      A: the continuity and initial-state equalities and the active inequality rows,
+ * then qbar = -v + cost_bar x, Pbar = -(v x' + x v')/2 + cost_bar x x'/2, an active row's bound gets its w, an inactive
+ * one 0, and everything is chained through the assembly to the inputs:
+ *   seg       [NUM_SEG_FIELDS][B][seg_stride]  fields 1-16; field 0 (T) is NOT differentiated: written as 0
+ *   init      [B][6]                           through the first segment's control points
+ *   ref_end   [B][2]                           through q's end term (its d_ref factor kept, as the assembly has it)
+ *   dl_bounds [B][10]
+ *   shared    [B][20] PER CANDIDATE, layout.Shared.as_array() order: w_s[4] w_l[4] weight_end_s weight_end_l ds_ref
+ *                     dl_ref dds[2] ddds[2] ddl[2] dddl[2]; delta and variant are not differentiated.  The caller sums
+ *                     the rows of a set.
+ * Inputs: the solve's own inputs (sets / n_sets / set_index as btrapz_solve_sets_device; one set: n_sets = 1 and
+ * set_index NULL, every candidate solved with sets[0]; seg_count NULL: uniform batch of seg_stride segments), and its
+ * outputs ctrl, status and lam = btrapz_warm.lam_out [2][36][B][seg_stride].  status MUST come from a solve with
+ * btrapz_options.elastic = 0: a rescued candidate solved a different problem.  The multipliers only classify the rows --
+ * a row is active when its multiplier exceeds its slack at x -- their values are not used.
+ * Defined cases:
+ *   - a candidate whose status is not 1 or 2, or that was not solved (set_index outside [0, n_sets), a segment count
+ *     outside 1..seg_stride), gets 0 in every entry;
+ *   - a bound that is no bound (|v| >= 1e9, moved out by the solve, or an acceleration / jerk limit the library moved:
+ *     beyond 1e9, or the s axis acceleration clamped to +-1000) gets 0;
+ *   - the cuboid variant's s axis interval max(0, bias, bias + skew t) / min(100, ...) gets the derivative of the branch
+ *     taken;
+ *   - a joint's position and velocity bound, stated by both segments (rows 0 / 6 of segment k+1 and rows 5 / 10 of
+ *     segment k), is one row with the intersection: its gradient goes to the field that supplied the tighter bound, on
+ *     an exact tie to segment k's.
+ * The active rows enter by the method of multipliers (relative penalty 1e6, three passes on one factorisation).
+ * Refused (BTRAPZ_EINVAL, btrapz_last_error says why): seg_stride > BTRAPZ_MAX_SEGMENTS (the long form keeps no
+ * multipliers), ctrl, lam or status NULL, ctrl_bar and cost_bar both NULL, sets of different variant or delta.
+ * Asynchronous and stream-ordered; the M'QM tables come from the context's cache of btrapz_solve_sets_device. */
+typedef struct btrapz_grads { /* DEVICE pointers, overwritten; any may be NULL (not wanted) */
+  double *seg;       /* [NUM_SEG_FIELDS][B][seg_stride] */
+  double *init;      /* [B][6] */
+  double *ref_end;   /* [B][2] */
+  double *dl_bounds; /* [B][10] */
+  double *shared;    /* [B][20] per candidate */
+} btrapz_grads;
+int btrapz_solve_vjp_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_sets, const int *set_index,
+                            int B, int seg_stride, const double *seg, const int *seg_count,
+                            const double *init, const double *ref_end, const double *dl_bounds,
+                            const double *ctrl, const double *lam, const int *status,
+                            const double *ctrl_bar, const double *cost_bar,
+                            const btrapz_grads *out, void *stream);
+
 /* State (p, v, a) of solved candidates at arbitrary times: x[b][axis][j] at times[b][j] seconds from the
  * start of candidate b's horizon (Bezier evaluation of solve_3d.cc:1366-1388; beyond the last segment the
  * end state is extrapolated at constant velocity).  With times = shift + the cumulative durations of the

@@ -79,6 +79,22 @@ struct KernelArgs {
   double *x_out;            // warm-start instantiations: joint states of the returned iterate, layout of x0 (may be null)
 };
 
+// btrapz_solve_vjp_device (btrapz_vjp.hip)
+struct VjpArgs {
+  int B, S, seg_stride;     // S: lanes per axis problem (the segment count of a uniform batch, seg_stride of a ragged one)
+  const int *seg_count;     // [B] or null
+  const Shared *sets;       // [n_sets] device view of the parameter sets
+  int n_sets;
+  const int *set_index;     // [B] or null (set 0)
+  const double *mqm;        // [n_sets][168] M'QM tables of the sets
+  const double *mqm_unit;   // [168] the same with every weight 1
+  const double *seg, *ref_end, *dl_bounds, *ctrl, *lam;
+  const int *status;
+  const double *ctrl_bar, *cost_bar;   // either may be null
+  double *g_seg, *g_init, *g_ref_end, *g_dl, *g_shared;   // any may be null
+};
+__global__ void vjp_kernel(const VjpArgs a);
+
 struct PrismRoad {              // btrapz_road in the form the prism stage uses it (prism_core.h)
   double rate;                  // knots per second (the reference hard-codes 10: `i/10`, `t0*10`)
   double s_lo, s_hi, l_lo, l_hi, l_safe, w_safe;

@@ -153,6 +153,7 @@ struct btrapz_ctx {
   Shared *h_sets_stage[2] = {nullptr, nullptr}; hipEvent_t sets_copied[2] = {nullptr, nullptr};
   bool sets_copy_pending[2] = {false, false}; int sets_stage_next = 0;
   int *d_sets_meta = nullptr; size_t sets_meta_cap = 0;   // bucket tables of a sets batch: [n_keys + 1] x 2 + [n_keys]
+  double *d_mqm_unit = nullptr;     // btrapz_solve_vjp_device: the M'QM table with every weight 1 ([2][4][21])
 };
 
 #define HIPCHK(ctx, call)                                                                     \
@@ -207,7 +208,7 @@ BTRAPZ_EXPORT int btrapz_destroy(btrapz_ctx *c) {
   (void)hipFree(c->d_queue); (void)hipFree(c->d_single_warm); (void)hipFree(c->d_susp_state); (void)hipFree(c->d_susp_ints);
   (void)hipFree(c->d_order); (void)hipFree(c->d_meta); (void)hipFree(c->d_retry); (void)hipFree(c->d_strips); (void)hipFree(c->d_corr_ws); (void)hipFree(c->d_long_list);
   (void)hipFree(c->d_rescue); (void)hipFree(c->d_rescue_meta); (void)hipFree(c->d_argmin_cost); (void)hipFree(c->d_argmin_idx);
-  (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets); (void)hipFree(c->d_sets_meta);
+  (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets); (void)hipFree(c->d_sets_meta); (void)hipFree(c->d_mqm_unit);
   for (int i = 0; i < 2; i++) {
     if (c->sets_copy_pending[i]) (void)hipEventSynchronize(c->sets_copied[i]);
     if (c->h_sets_stage[i]) (void)hipHostFree(c->h_sets_stage[i]);
@@ -789,6 +790,51 @@ BTRAPZ_EXPORT int btrapz_solve_warm_device(btrapz_ctx *c, const btrapz_shared *s
                       iters, stream);
 }
 
+// The device view of the sets and their M'QM tables (btrapz_solve_sets_device, btrapz_solve_vjp_device), kept by the
+// context and rebuilt, stream-ordered, only when the sets change.
+static int sets_tables(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, hipStream_t stream) {
+  // the sets as the kernels read them (fill_parameters' limits), padding zeroed so that the cache can compare bytes
+  std::vector<Shared> h((size_t)n_sets);
+  for (int g = 0; g < n_sets; g++) {
+    KernelArgs t;
+    memset(&t, 0, sizeof(t));
+    fill_parameters(t, &sets[g], nullptr, nullptr);
+    memcpy(&h[(size_t)g], &t.sh, sizeof(Shared));
+  }
+  if (h.size() != c->h_sets.size() || memcmp(h.data(), c->h_sets.data(), sizeof(Shared) * h.size()) != 0) {
+    c->h_sets.clear();   // (until the new tables are enqueued)
+    if ((size_t)n_sets > c->sets_cap) {
+      for (int i = 0; i < 2; i++) {
+        if (c->sets_copy_pending[i]) { HIPCHK(c, hipEventSynchronize(c->sets_copied[i])); c->sets_copy_pending[i] = false; }
+        (void)hipHostFree(c->h_sets_stage[i]); c->h_sets_stage[i] = nullptr;
+      }
+      (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets);
+      c->d_sets = nullptr; c->d_mqm_sets = nullptr; c->sets_cap = 0;
+      const size_t cap = (size_t)BTRAPZ_MAX_SETS < 64 * (((size_t)n_sets + 63) / 64) ? (size_t)BTRAPZ_MAX_SETS : 64 * (((size_t)n_sets + 63) / 64);
+      HIPCHK(c, hipMalloc(&c->d_sets, sizeof(Shared) * cap));
+      HIPCHK(c, hipMalloc(&c->d_mqm_sets, sizeof(double) * 168 * cap));
+      for (int i = 0; i < 2; i++) HIPCHK(c, hipHostMalloc((void **)&c->h_sets_stage[i], sizeof(Shared) * cap, hipHostMallocDefault));
+      c->sets_cap = cap;
+    }
+    // Two staging buffers in turn: a buffer is rewritten once ITS copy -- that of the change before the previous one -- has
+    // left it.  The copy itself is stream-ordered behind the launches that still read the device tables (same stream, or
+    // the ws_free event above), so a loop whose sets change at every step waits for the device only when it is two
+    // changes ahead of it.
+    const int si = c->sets_stage_next;
+    c->sets_stage_next = 1 - si;
+    if (!c->sets_copied[si]) HIPCHK(c, hipEventCreateWithFlags(&c->sets_copied[si], hipEventDisableTiming));
+    if (c->sets_copy_pending[si]) HIPCHK(c, hipEventSynchronize(c->sets_copied[si]));
+    memcpy(c->h_sets_stage[si], h.data(), sizeof(Shared) * h.size());
+    HIPCHK(c, hipMemcpyAsync(c->d_sets, c->h_sets_stage[si], sizeof(Shared) * h.size(), hipMemcpyHostToDevice, stream));
+    HIPCHK(c, hipEventRecord(c->sets_copied[si], stream));
+    c->sets_copy_pending[si] = true;
+    hipLaunchKernelGGL(mqm_sets_kernel, dim3((unsigned)n_sets), dim3(192), 0, stream, (const Shared *)c->d_sets, c->d_mqm_sets);
+    HIPCHK(c, hipGetLastError());
+    c->h_sets.swap(h);
+  }
+  return BTRAPZ_OK;
+}
+
 // A parameter set per candidate (btrapz_solve_sets_device).  The sets' device view and M'QM tables live in the context,
 // cached by content: a loop that passes the same sets every step copies and builds nothing.  The candidates are bucketed
 // on the device by (set, segment count) -- btrapz_sets.hip -- and solved in ONE launch of an ordered instantiation whose
@@ -833,45 +879,8 @@ BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *s
   if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
   int rc = ensure_axis_ws(c, 2 * (size_t)B);
   if (rc != BTRAPZ_OK) return rc;
-  // the sets as the kernels read them (fill_parameters' limits), padding zeroed so that the cache can compare bytes
-  std::vector<Shared> h((size_t)n_sets);
-  for (int g = 0; g < n_sets; g++) {
-    KernelArgs t;
-    memset(&t, 0, sizeof(t));
-    fill_parameters(t, &sets[g], opt, nullptr);
-    memcpy(&h[(size_t)g], &t.sh, sizeof(Shared));
-  }
-  if (h.size() != c->h_sets.size() || memcmp(h.data(), c->h_sets.data(), sizeof(Shared) * h.size()) != 0) {
-    c->h_sets.clear();   // (until the new tables are enqueued)
-    if ((size_t)n_sets > c->sets_cap) {
-      for (int i = 0; i < 2; i++) {
-        if (c->sets_copy_pending[i]) { HIPCHK(c, hipEventSynchronize(c->sets_copied[i])); c->sets_copy_pending[i] = false; }
-        (void)hipHostFree(c->h_sets_stage[i]); c->h_sets_stage[i] = nullptr;
-      }
-      (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets);
-      c->d_sets = nullptr; c->d_mqm_sets = nullptr; c->sets_cap = 0;
-      const size_t cap = (size_t)BTRAPZ_MAX_SETS < 64 * (((size_t)n_sets + 63) / 64) ? (size_t)BTRAPZ_MAX_SETS : 64 * (((size_t)n_sets + 63) / 64);
-      HIPCHK(c, hipMalloc(&c->d_sets, sizeof(Shared) * cap));
-      HIPCHK(c, hipMalloc(&c->d_mqm_sets, sizeof(double) * 168 * cap));
-      for (int i = 0; i < 2; i++) HIPCHK(c, hipHostMalloc((void **)&c->h_sets_stage[i], sizeof(Shared) * cap, hipHostMallocDefault));
-      c->sets_cap = cap;
-    }
-    // Two staging buffers in turn: a buffer is rewritten once ITS copy -- that of the change before the previous one -- has
-    // left it.  The copy itself is stream-ordered behind the launches that still read the device tables (same stream, or
-    // the ws_free event above), so a loop whose sets change at every step waits for the device only when it is two
-    // changes ahead of it.
-    const int si = c->sets_stage_next;
-    c->sets_stage_next = 1 - si;
-    if (!c->sets_copied[si]) HIPCHK(c, hipEventCreateWithFlags(&c->sets_copied[si], hipEventDisableTiming));
-    if (c->sets_copy_pending[si]) HIPCHK(c, hipEventSynchronize(c->sets_copied[si]));
-    memcpy(c->h_sets_stage[si], h.data(), sizeof(Shared) * h.size());
-    HIPCHK(c, hipMemcpyAsync(c->d_sets, c->h_sets_stage[si], sizeof(Shared) * h.size(), hipMemcpyHostToDevice, stream));
-    HIPCHK(c, hipEventRecord(c->sets_copied[si], stream));
-    c->sets_copy_pending[si] = true;
-    hipLaunchKernelGGL(mqm_sets_kernel, dim3((unsigned)n_sets), dim3(192), 0, stream, (const Shared *)c->d_sets, c->d_mqm_sets);
-    HIPCHK(c, hipGetLastError());
-    c->h_sets.swap(h);
-  }
+  rc = sets_tables(c, sets, n_sets, stream);
+  if (rc != BTRAPZ_OK) return rc;
   KernelArgs a;
   fill_parameters(a, &sets[0], opt, warm);   // (a.sh is not read: every wavefront reads its own set)
   a.B = B; a.S = S; a.seg_stride = S;
@@ -976,6 +985,64 @@ BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *s
   }
   hipLaunchKernelGGL(finalize_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, c->d_axis_obj, c->d_axis_status,
                      c->d_axis_iters, cost, status, iters);
+  HIPCHK(c, hipGetLastError());
+  c->ws_stream = stream; c->ws_used = true;
+  HIPCHK(c, hipEventRecord(c->ws_free, stream));
+  return BTRAPZ_OK;
+}
+
+// Gradients of a solve (btrapz_solve_vjp_device): one launch of vjp_kernel (btrapz_vjp.hip), groups of S lanes as the
+// packed solve lays them out -- S = seg_stride for a ragged batch, whose lanes beyond a candidate's count stay idle.
+BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                       int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                       const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                       const int *status, const double *ctrl_bar, const double *cost_bar,
+                                       const btrapz_grads *out, void *stream_) {
+  (void)init;   // (the initial state enters the gradient through the returned control points of segment 0)
+  if (!c) return BTRAPZ_EINVAL;
+  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds || !out) {
+    c->err = "invalid argument (vjp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays and out non-null)";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS) {
+    c->err = "invalid argument: vjp of candidates of at most BTRAPZ_MAX_SEGMENTS segments (the long form keeps no multipliers)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl || !lam || !status) {
+    c->err = "invalid argument: vjp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl_bar && !cost_bar) {
+    c->err = "invalid argument: vjp needs ctrl_bar or cost_bar (both NULL)";
+    return BTRAPZ_EINVAL;
+  }
+  for (int g = 1; g < n_sets; g++)
+    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
+      c->err = "invalid argument: every parameter set must have the same variant and delta";
+      return BTRAPZ_EINVAL;
+    }
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  int rc = sets_tables(c, sets, n_sets, stream);
+  if (rc != BTRAPZ_OK) return rc;
+  if (!c->d_mqm_unit) {
+    HIPCHK(c, hipMalloc(&c->d_mqm_unit, sizeof(double) * 168));
+    MqmWeights ones;
+    for (int ax = 0; ax < 2; ax++)
+      for (int d = 0; d < 4; d++) ones.w[ax][d] = 1.0;
+    hipLaunchKernelGGL(mqm_table_kernel, dim3(1), dim3(192), 0, stream, ones, c->d_mqm_unit);
+    HIPCHK(c, hipGetLastError());
+  }
+  VjpArgs a;
+  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.seg_count = seg_count;
+  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
+  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
+  a.ctrl_bar = ctrl_bar; a.cost_bar = cost_bar;
+  a.g_seg = out->seg; a.g_init = out->init; a.g_ref_end = out->ref_end; a.g_dl = out->dl_bounds; a.g_shared = out->shared;
+  const unsigned gpw = 64u / (unsigned)seg_stride;
+  const unsigned blocks = 2u * (unsigned)(((size_t)B + gpw - 1) / gpw);
+  hipLaunchKernelGGL(vjp_kernel, dim3(blocks), dim3(64), 0, stream, a);
   HIPCHK(c, hipGetLastError());
   c->ws_stream = stream; c->ws_used = true;
   HIPCHK(c, hipEventRecord(c->ws_free, stream));

@@ -54,6 +54,12 @@ def _options(max_iter=0, eps=0.0, elastic=0, elastic_tol=0.0, elastic_delta=0.0,
                     float(elastic_delta), int(queue), int(split), int(start), int(cap_iter), int(lean), int(compact))
 
 
+class CGrads(C.Structure):
+    """btrapz_grads (include/btrapz_hip.h): device pointers of the gradient arrays of btrapz_solve_vjp_device."""
+    _fields_ = [("seg", C.c_void_p), ("init", C.c_void_p), ("ref_end", C.c_void_p), ("dl_bounds", C.c_void_p),
+                ("shared", C.c_void_p)]
+
+
 class CWarm(C.Structure):
     """btrapz_warm (include/btrapz_hip.h): optional warm start of a solve."""
     _fields_ = [("x0", C.c_void_p), ("lam0", C.c_void_p), ("lam_out", C.c_void_p),
@@ -121,7 +127,7 @@ EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "bt
            "btrapz_device_count", "btrapz_solve_batch_device", "btrapz_argmin_device",
            "btrapz_sample_device", "btrapz_solve_batch_host", "btrapz_solve_ragged_device",
            "btrapz_corridor_batch_device", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
-           "btrapz_solve_sets_device", "btrapz_eval_states_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
+           "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_eval_states_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
            "btrapz_prism_corridor_batch_device",
            "btrapz_find_traj_last_iterations", "btrapz_argmin_pairs_device", "btrapz_options_init",
            "btrapz_rescue_violations_device", "btrapz_find_traj_last_status", "btrapz_debug_mqm_tables",
@@ -220,6 +226,8 @@ def lib():
                                                C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
         l.btrapz_solve_sets_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.POINTER(COptions), C.POINTER(CWarm),
                                                C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
+        l.btrapz_solve_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, dp,
+                                              dp, dp, ip, dp, dp, C.POINTER(CGrads), vp]
         l.btrapz_eval_states_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, vp]
         l.btrapz_prism_bounds_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, ip, vp]
         l.btrapz_prism_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int,
@@ -454,6 +462,21 @@ class Context:
                                                    ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
                                                    ptr(cost), ptr(status), ptr(iters), C.c_void_p(stream or 0)),
                     "btrapz_solve_sets_device")
+
+    def solve_vjp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                         ctrl_bar, cost_bar, g_seg=None, g_init=None, g_ref_end=None, g_dl_bounds=None, g_shared=None,
+                         stream=None):
+        """btrapz_solve_vjp_device: gradients of a solve (elastic = 0, multipliers kept) w.r.t. its inputs.  sets = list of
+        layout.Shared; set_index None = every candidate with sets[0]; seg_count None = uniform batch; ctrl_bar / cost_bar
+        may be None (zero); the g_* device tensors are overwritten (None: not wanted)."""
+        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
+        raw = lambda t: t.data_ptr() if t is not None else None
+        grads = CGrads(raw(g_seg), raw(g_init), raw(g_ref_end), raw(g_dl_bounds), raw(g_shared))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_solve_vjp_device(self._h, arr, len(sets), ptr(set_index), B, seg_stride, ptr(seg),
+                                                  ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
+                                                  ptr(lam), ptr(status), ptr(ctrl_bar), ptr(cost_bar), C.byref(grads),
+                                                  C.c_void_p(stream or 0)), "btrapz_solve_vjp_device")
 
     def workspace_bytes(self):
         """btrapz_workspace_bytes: device memory the context holds for its launches right now."""

@@ -223,6 +223,40 @@ class BatchSolver:
                  status=torch.empty(B, dtype=torch.int32, device=d), iters=torch.empty(B, dtype=torch.int32, device=d))
         return self._sets_call(B, st, sets, set_index, rec, rec["seg_count"], o, warm, keep_multipliers, options)
 
+    def solve_vjp(self, dbatch_or_rec, shared_or_sets, out, ctrl_bar, cost_bar, set_index=None):
+        """Gradients of a solve (btrapz_solve_vjp_device).  dbatch_or_rec: the DeviceBatch or ragged record that was solved;
+        shared_or_sets: its layout.Shared, or the list of sets with set_index (int32 device tensor [B]); out: the solve's
+        result dict, from a solve with keep_multipliers=True and elastic=0 (needs "ctrl", "lam", "status"); ctrl_bar
+        [B, 12 S] / cost_bar [B]: cotangents (either may be None).  Returns a dict of device tensors: "seg"
+        [NUM_SEG_FIELDS, B, S] (field 0 is 0), "init" [B, 6], "ref_end" [B, 2], "dl_bounds" [B, 10], "shared" [B, 20] per
+        candidate (layout.Shared.as_array order, without delta)."""
+        if isinstance(dbatch_or_rec, dict):
+            B, S, seg_count = dbatch_or_rec["B"], dbatch_or_rec["seg_stride"], dbatch_or_rec["seg_count"]
+            seg, init, ref_end, dl = (dbatch_or_rec[k] for k in ("seg", "init", "ref_end", "dl_bounds"))
+        else:
+            B, S, seg_count = dbatch_or_rec.B, dbatch_or_rec.S, None
+            seg, init, ref_end, dl = dbatch_or_rec.seg, dbatch_or_rec.init, dbatch_or_rec.ref_end, dbatch_or_rec.dl_bounds
+        sets = list(shared_or_sets) if isinstance(shared_or_sets, (list, tuple)) else [shared_or_sets]
+        if set_index is not None:
+            assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
+        if out.get("lam") is None:
+            raise ValueError("solve_vjp needs the solve's multipliers: solve with keep_multipliers=True")
+        chk = lambda t, shape: None if t is None else (t if (t.dtype == torch.float64 and t.is_contiguous() and
+                                                            tuple(t.shape) == shape) else
+                                                       t.to(self.device, dtype=torch.float64).reshape(shape).contiguous())
+        ctrl_bar = chk(ctrl_bar, (B, 12 * S)); cost_bar = chk(cost_bar, (B,))
+        d = self.device
+        g = dict(seg=torch.empty((L.NUM_SEG_FIELDS, B, S), dtype=torch.float64, device=d),
+                 init=torch.empty((B, 6), dtype=torch.float64, device=d),
+                 ref_end=torch.empty((B, 2), dtype=torch.float64, device=d),
+                 dl_bounds=torch.empty((B, 10), dtype=torch.float64, device=d),
+                 shared=torch.empty((B, 20), dtype=torch.float64, device=d))
+        stream = torch.cuda.current_stream(d).cuda_stream
+        self.ctx.solve_vjp_device(B, S, sets, set_index, seg, seg_count, init, ref_end, dl, out["ctrl"], out["lam"],
+                                  out["status"], ctrl_bar, cost_bar, g_seg=g["seg"], g_init=g["init"],
+                                  g_ref_end=g["ref_end"], g_dl_bounds=g["dl_bounds"], g_shared=g["shared"], stream=stream)
+        return g
+
     def argmin(self, cost, group=None, index_base=0):
         """Arg-min of cost over contiguous groups (default: the whole batch). Device tensors."""
         B = cost.numel()

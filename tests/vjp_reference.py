@@ -1,0 +1,180 @@
+"""Yardstick of btrapz_solve_vjp_device: the gradients of one candidate's QP from the oracle's dense assembly.
+
+x*, y* from the oracle's exact solver; the active set from y* (equality rows always); the adjoint KKT system
+    [ P  A_act' ] [v]   [xbar + cbar (P x + q)]
+    [ A_act  0  ] [w] = [          0          ]
+by least squares; then dL/dtheta = (-v + cbar x)' dq + (-v' dP x + cbar x' dP x / 2) + sum_act w_i db_i, with dP, dq, db
+the central differences of the ASSEMBLY (not of the solve) -- exact to rounding where the assembly is linear in the
+field, which it is in every differentiated field except the cuboid variant's max / min.  A segment field is perturbed
+in all segments at once and its changes attributed by segment: every row and entry of q / P belongs to one segment.
+"""
+import dataclasses
+
+import numpy as np
+
+from helpers import oracle_qp_from_batch
+from spectral_amd import layout as L
+
+SEG_FIELDS = list(range(1, L.NUM_SEG_FIELDS))   # field 0 (T) is not differentiated
+PARAM_NAMES = [("w_s", 0), ("w_s", 1), ("w_s", 2), ("w_s", 3), ("w_l", 0), ("w_l", 1), ("w_l", 2), ("w_l", 3),
+               ("weight_end_s", None), ("weight_end_l", None), ("ds_ref", None), ("dl_ref", None), ("dds", 0), ("dds", 1),
+               ("ddds", 0), ("ddds", 1), ("ddl", 0), ("ddl", 1), ("dddl", 0), ("dddl", 1)]
+
+
+def one(batch, b):
+    """Candidate b as a batch of its own, in arrays of its own (a slice can be a view)."""
+    c = batch.slice(b, b + 1)
+    return L.Batch(B=1, S=c.S, seg=c.seg.copy(), init=c.init.copy(), ref_end=c.ref_end.copy(), dl_bounds=c.dl_bounds.copy())
+
+
+def shared_with(sh, j, delta):
+    name, i = PARAM_NAMES[j]
+    if i is None:
+        return dataclasses.replace(sh, **{name: getattr(sh, name) + delta})
+    v = list(getattr(sh, name)); v[i] += delta
+    return dataclasses.replace(sh, **{name: tuple(v)})
+
+
+def dense(batch, sh):
+    qp = oracle_qp_from_batch(batch, sh, 0)
+    P, A = qp.dense()
+    return qp, P, A, np.array(qp.q), np.array(qp.l), np.array(qp.u)
+
+
+class Adjoint:
+    """The adjoint solution of candidate 0 of a one-candidate batch, and its degeneracy diagnostics."""
+
+    def __init__(self, batch, sh, xbar, cbar, margin=1e-6):
+        self.batch, self.sh, self.S = batch, sh, batch.S
+        qp, P, A, q, l, u = dense(batch, sh)
+        x, y, info = qp.solve_exact()
+        self.status = int(info.status_val) if hasattr(info, "status_val") else 1
+        self.P, self.A, self.q, self.l, self.u, self.x, self.y = P, A, q, l, u, x, y
+        self.cbar = float(cbar)
+        xb = np.asarray(xbar, dtype=float) + self.cbar * (P @ x + q)
+        Ax = A @ x
+        eq = (u - l) <= 1e-12
+        ymax = max(np.abs(y).max(), 1e-300)
+        scale = 1.0 + np.maximum(np.abs(np.where(np.abs(l) < 1e9, l, 0)), np.abs(np.where(np.abs(u) < 1e9, u, 0)))
+        act = eq | (np.abs(y) > margin * ymax)
+        slack = np.minimum(Ax - l, u - Ax)
+        # strict complementarity: every inequality row clearly active or clearly inactive
+        self.strict = bool(np.all(eq | (np.abs(y) > margin * ymax) | (slack > margin * scale)))
+        self.lower = (~eq) & act & (np.abs(Ax - l) <= np.abs(u - Ax))
+        self.act = act
+        Aa = A[act]
+        n, ma = P.shape[0], Aa.shape[0]
+        K = np.zeros((n + ma, n + ma))
+        K[:n, :n] = P; K[:n, n:] = Aa.T; K[n:, :n] = Aa
+        sol = np.linalg.lstsq(K, np.concatenate([xb, np.zeros(ma)]), rcond=None)[0]
+        self.v = sol[:n]
+        self.w = np.zeros(A.shape[0]); self.w[act] = sol[n:]
+        # left null space of the active rows: where it is not empty (a joint's two rows both active, an initial-state row
+        # active at the given state) w is not unique, and a gradient is only where its bound derivatives see none of it
+        U_, sv, _ = np.linalg.svd(Aa, full_matrices=True)
+        rank = int((sv > 1e-9 * max(1.0, sv.max() if sv.size else 1.0)).sum())
+        self.null = U_[:, rank:]
+        self.full_rank = rank == ma
+        self.unique = True
+        self.ambiguous = set()   # (array, index...) of the gradients that are not unique
+        # segment of every variable and row (the columns a row touches all belong to one segment, or -- continuity -- to
+        # two neighbours: such rows have no field-dependent bound)
+        S = self.S
+        self.var_seg = (np.arange(n) % (6 * S)) // 6
+        first_col = np.argmax(A != 0, axis=1)
+        self.row_seg = self.var_seg[first_col]
+
+    @property
+    def nondegenerate(self):
+        """Strict complementarity, and every gradient unique (no two different fields tie at a joint).  Valid after
+        grads()."""
+        return self.strict and self.unique
+
+    def _check_unique(self, db_rows, key):
+        if self.null.shape[1] == 0:
+            return
+        d = db_rows[self.act]
+        if np.abs(self.null.T @ d).max() > 1e-7 * max(1.0, np.abs(d).max()):
+            self.unique = False
+            self.ambiguous.add(key)
+
+    def unique_mask(self):
+        """Boolean arrays shaped like grads(): True where the gradient is unique (valid after grads())."""
+        m = dict(seg=np.ones((L.NUM_SEG_FIELDS, self.S), bool), init=np.ones(6, bool), ref_end=np.ones(2, bool),
+                 dl_bounds=np.ones(10, bool), shared=np.ones(20, bool))
+        for key in self.ambiguous:
+            m[key[0]][key[1:]] = False
+        return m
+
+    def contributions(self, dP, dq, dl, du):
+        """Per-variable and per-row pieces of dL for one direction of the assembly's change."""
+        v, x, c = self.v, self.x, self.cbar
+        var_part = (-v + c * x) * dq + (-(dP @ x) * v + 0.5 * c * (dP @ x) * x)
+        db = np.where(self.lower | ((self.u - self.l) <= 1e-12), dl, du)
+        row_part = np.where(self.act, self.w * db, 0.0)
+        self._db = db
+        return var_part, row_part
+
+    def _diff(self, plus, minus, h):
+        _, Pp, Ap, qp_, lp, up = dense(*plus)
+        _, Pm, Am, qm, lm, um = dense(*minus)
+        fin = lambda a, b_: np.where((np.abs(a) < 1e9) & (np.abs(b_) < 1e9), a - b_, 0.0)
+        return (Pp - Pm) / (2 * h), (qp_ - qm) / (2 * h), fin(lp, lm) / (2 * h), fin(up, um) / (2 * h)
+
+    def grads(self, h=1e-6):
+        """dL/dtheta for every differentiated input: dict seg [17][S], init [6], ref_end [2], dl_bounds [10], shared [20]."""
+        bt, sh, S = self.batch, self.sh, self.S
+        out = dict(seg=np.zeros((L.NUM_SEG_FIELDS, S)), init=np.zeros(6), ref_end=np.zeros(2), dl_bounds=np.zeros(10),
+                   shared=np.zeros(20))
+
+        def moved(attr, idx, hh):
+            p = one(bt, 0); m = one(bt, 0)
+            getattr(p, attr)[idx] += hh; getattr(m, attr)[idx] -= hh
+            return (p, sh), (m, sh)
+
+        for f in SEG_FIELDS:
+            vals = bt.seg[f, 0]
+            hk = h * (1.0 + np.abs(vals))
+            p = one(bt, 0); m = one(bt, 0)
+            p.seg[f, 0] += hk; m.seg[f, 0] -= hk
+            dP, dq, dl, du = self._diff((p, sh), (m, sh), 1.0)
+            vp, rp = self.contributions(dP, dq, dl, du)
+            for k in range(S):
+                out["seg"][f, k] = (vp[self.var_seg == k].sum() + rp[self.row_seg == k].sum()) / hk[k]
+                self._check_unique(np.where(self.row_seg == k, self._db, 0.0), ("seg", f, k))
+        if sh.variant == 1:
+            # the cuboid s axis interval max(0, max_i bias + skew (i/5) t) / min(100, ...) has a kink where its branches
+            # tie (skew 0, or the clamp exactly reached): the central difference averages two one-sided derivatives
+            t = bt.seg[L.F_T, 0]
+            for fb, fs, clamp in ((L.F_DOWN_BIAS, L.F_DOWN_SKEW, 0.0), (L.F_UPP_BIAS, L.F_UPP_SKEW, 100.0)):
+                for k in range(S):
+                    b0, s0 = bt.seg[fb, 0, k], bt.seg[fs, 0, k]
+                    inner = max(b0, b0 + s0 * t[k]) if clamp == 0.0 else min(b0, b0 + s0 * t[k])
+                    if s0 == 0.0 or inner == clamp:
+                        self.ambiguous.update({("seg", fb, k), ("seg", fs, k)}); self.unique = False
+        for attr, n_ in (("init", 6), ("ref_end", 2), ("dl_bounds", 10)):
+            for i in range(n_):
+                hh = h * (1.0 + abs(getattr(bt, attr)[0, i]))
+                plus, minus = moved(attr, (0, i), hh)
+                vp, rp = self.contributions(*self._diff(plus, minus, hh))
+                out[attr][i] = vp.sum() + rp.sum()
+                self._check_unique(self._db, (attr, i))
+        arr = sh.as_array()
+        for j in range(20):
+            hh = h * (1.0 + abs(arr[j]))
+            vp, rp = self.contributions(*self._diff((bt, shared_with(sh, j, hh)), (bt, shared_with(sh, j, -hh)), hh))
+            out["shared"][j] = vp.sum() + rp.sum()
+            self._check_unique(self._db, ("shared", j))
+        return out
+
+
+def reference_vjp(batch, sh, b, xbar, cbar, h=1e-6):
+    """(grads, Adjoint) of candidate b of a batch for cotangents xbar [12 S] and cbar."""
+    adj = Adjoint(one(batch, b), sh, xbar, cbar)
+    return adj.grads(h), adj
+
+
+def exact_x(batch, sh, b=0):
+    qp = oracle_qp_from_batch(batch, sh, b)
+    x, y, info = qp.solve_exact()
+    return x, 0.5 * x @ (qp.dense()[0] @ x) + np.dot(qp.q, x)
