@@ -573,6 +573,47 @@ int btrapz_solve_vjp_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_se
                             const double *ctrl_bar, const double *cost_bar,
                             const btrapz_grads *out, void *stream);
 
+/* ---- trajectory scores (a_cost) and their gradients ------------------------------------------------------------------
+ * a_cost[b] is what find_traj returns for a trajectory (trp_wrapper.cpp:207-286 / cub_wrapper.cpp:201-262, restated in
+ * traj_cost.h) on the samples btrapz_sample_device produces from ctrl[b]: sample 0 is init[b], samples 1..total the
+ * Bernstein samples (total = sum of (int)(t_k / delta)), reads of s_ref[i] / l_ref[i] clamped to N - 1, the first jerk
+ * (dds[1] - dds[0]) / delta, the trapezoid's end term weight_end_l (l[min(N - 1, np - 1)] - l_ref[N - 1])^2 delta; the
+ * cuboid variant uses no weights.  n_points[b] (may be NULL) receives the sample count np = total + 1.
+ *   sets / n_sets / set_index: the SCORING weights, as btrapz_solve_sets_device takes them (one set: set_index NULL);
+ *     variant and delta come from the sets and must agree.  To reproduce find_traj, pass the sets of the solve.
+ *   seg_count NULL: uniform batch of seg_stride <= BTRAPZ_MAX_SEGMENTS_LONG segments; else ragged.
+ *   s_ref, l_ref [B][N] with ref_stride = N, or [N] for every candidate with ref_stride = 0.
+ *   status (may be NULL): candidates whose status is not 1 or 2 are not scored.
+ * Not scored -- a_cost = +inf (what btrapz_argmin_device skips), n_points = 0, zero gradients: a status outside {1, 2},
+ * a segment count outside 1..seg_stride, a set_index outside [0, n_sets), a segment duration that is not > 0, or a failed
+ * sample-count check (np accumulated in double against the int sum, solve_3d.cc:1407): what makes find_traj fail.  A
+ * reference line that is not finite gives NaN, as the reference does.
+ * Refused (BTRAPZ_EINVAL, btrapz_last_error says why): ctrl, seg, init, s_ref or l_ref NULL; B < 1 or N < 1;
+ * seg_stride > BTRAPZ_MAX_SEGMENTS_LONG; sets of different variant or delta; ref_stride other than N or 0; a_cost NULL
+ * (a_cost_bar NULL in the VJP).  Asynchronous and stream-ordered; no host round trip. */
+int btrapz_traj_cost_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_sets, const int *set_index,
+                            int B, int seg_stride, const double *seg, const int *seg_count,
+                            const double *init, const double *ctrl, const int *status,
+                            int N, const double *s_ref, const double *l_ref, int ref_stride,
+                            double *a_cost, int *n_points, void *stream);
+/* Vector-Jacobian product of btrapz_traj_cost_device: given a_cost_bar [B], the direct derivative of the score (a sum of
+ * per-sample terms; no solve is involved).  DEVICE outputs, overwritten; any may be NULL (not wanted):
+ *   ctrl_bar   [B][12 seg_stride]  through the Bernstein sampling (linear in ctrl); slots beyond 12 S_b are 0
+ *   init_bar   [B][6]              the derivative with respect to sample 0
+ *   params_bar [B][20]             layout.Shared.as_array() order, as btrapz_grads.shared: the trapezoid's
+ *                                  sum e^2 delta, ds^2 delta, dds^2 delta, jerk^2 delta per axis (0-7) and the end term (9);
+ *                                  the other entries, and every entry of the cuboid variant, are 0
+ *   s_ref_bar, l_ref_bar [B][N]    PER CANDIDATE even when ref_stride = 0 (the caller sums the rows: no atomics)
+ * The durations (field 0, and hence the sample count) are not differentiated.  Clamped reads accumulate on s_ref[N - 1] /
+ * l_ref[N - 1].  The cuboid's max terms are differentiated at the first index that attains the maximum; |x| at 0 has
+ * derivative 0.  Candidates that are not scored get 0 everywhere. */
+int btrapz_traj_cost_vjp_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                int B, int seg_stride, const double *seg, const int *seg_count,
+                                const double *init, const double *ctrl, const int *status,
+                                int N, const double *s_ref, const double *l_ref, int ref_stride,
+                                const double *a_cost_bar, double *ctrl_bar, double *init_bar, double *params_bar,
+                                double *s_ref_bar, double *l_ref_bar, void *stream);
+
 /* State (p, v, a) of solved candidates at arbitrary times: x[b][axis][j] at times[b][j] seconds from the
  * start of candidate b's horizon (Bezier evaluation of solve_3d.cc:1366-1388; beyond the last segment the
  * end state is extrapolated at constant velocity).  With times = shift + the cumulative durations of the

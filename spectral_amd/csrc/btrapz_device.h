@@ -95,6 +95,27 @@ struct VjpArgs {
 };
 __global__ void vjp_kernel(const VjpArgs a);
 
+// btrapz_traj_cost_device / btrapz_traj_cost_vjp_device (btrapz_acost.hip)
+struct AcostArgs {
+  int B, seg_stride;
+  const int *seg_count;     // [B] or null (uniform)
+  const Shared *sets;       // [n_sets] device view of the scoring sets
+  int n_sets;
+  const int *set_index;     // [B] or null (set 0)
+  const double *seg, *init, *ctrl;
+  const int *status;        // [B] or null (every candidate with a valid count)
+  int N, ref_stride;        // ref_stride: N or 0
+  const double *s_ref, *l_ref;
+  double delta;
+  int variant;
+  double *a_cost;           // [B]
+  int *n_points;            // [B] or null
+  const double *a_cost_bar; // VJP: [B]
+  double *ctrl_bar, *init_bar, *params_bar, *s_ref_bar, *l_ref_bar;   // VJP outputs, any may be null
+};
+__global__ void acost_kernel(const AcostArgs a);
+__global__ void acost_vjp_kernel(const AcostArgs a);
+
 struct PrismRoad {              // btrapz_road in the form the prism stage uses it (prism_core.h)
   double rate;                  // knots per second (the reference hard-codes 10: `i/10`, `t0*10`)
   double s_lo, s_hi, l_lo, l_hi, l_safe, w_safe;

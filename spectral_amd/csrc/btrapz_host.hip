@@ -1049,6 +1049,91 @@ BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *se
   return BTRAPZ_OK;
 }
 
+// a_cost of sampled trajectories and its VJP (btrapz_traj_cost_device, btrapz_traj_cost_vjp_device): one workgroup of 64
+// per candidate (btrapz_acost.hip); the scoring sets come from the context's cache of btrapz_solve_sets_device.
+static int traj_cost_common(btrapz_ctx *c, bool vjp, const btrapz_shared *sets, int n_sets, const int *set_index, int B,
+                            int seg_stride, const double *seg, const int *seg_count, const double *init, const double *ctrl,
+                            const int *status, int N, const double *s_ref, const double *l_ref, int ref_stride,
+                            double *a_cost, int *n_points, const double *a_cost_bar, double *ctrl_bar, double *init_bar,
+                            double *params_bar, double *s_ref_bar, double *l_ref_bar, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS) {
+    c->err = "invalid argument: 1 <= n_sets <= BTRAPZ_MAX_SETS and sets non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl || !seg || !init || !s_ref || !l_ref) {
+    c->err = "invalid argument: ctrl, seg, init, s_ref and l_ref must be non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (B < 1 || N < 1 || seg_stride < 1) {
+    c->err = "invalid argument: B >= 1, N >= 1 and seg_stride >= 1";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: seg_stride > BTRAPZ_MAX_SEGMENTS_LONG";
+    return BTRAPZ_EINVAL;
+  }
+  for (int g = 1; g < n_sets; g++)
+    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
+      c->err = "invalid argument: every parameter set must have the same variant and delta";
+      return BTRAPZ_EINVAL;
+    }
+  if (sets[0].variant != BTRAPZ_TRAPEZOID && sets[0].variant != BTRAPZ_CUBOID) {
+    c->err = "invalid argument: variant";
+    return BTRAPZ_EINVAL;
+  }
+  if (ref_stride != N && ref_stride != 0) {
+    c->err = "invalid argument: ref_stride must be N (a reference line per candidate) or 0 (one line for all)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!vjp && !a_cost) {
+    c->err = "invalid argument: a_cost is null";
+    return BTRAPZ_EINVAL;
+  }
+  if (vjp && !a_cost_bar) {
+    c->err = "invalid argument: a_cost_bar is null";
+    return BTRAPZ_EINVAL;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  int rc = sets_tables(c, sets, n_sets, stream);
+  if (rc != BTRAPZ_OK) return rc;
+  AcostArgs a;
+  a.B = B; a.seg_stride = seg_stride; a.seg_count = seg_count;
+  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index;
+  a.seg = seg; a.init = init; a.ctrl = ctrl; a.status = status;
+  a.N = N; a.ref_stride = ref_stride; a.s_ref = s_ref; a.l_ref = l_ref;
+  a.delta = sets[0].delta; a.variant = sets[0].variant;
+  a.a_cost = a_cost; a.n_points = n_points; a.a_cost_bar = a_cost_bar;
+  a.ctrl_bar = ctrl_bar; a.init_bar = init_bar; a.params_bar = params_bar; a.s_ref_bar = s_ref_bar; a.l_ref_bar = l_ref_bar;
+  if (vjp) hipLaunchKernelGGL(acost_vjp_kernel, dim3((unsigned)B), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(acost_kernel, dim3((unsigned)B), dim3(64), 0, stream, a);
+  HIPCHK(c, hipGetLastError());
+  c->ws_stream = stream; c->ws_used = true;
+  HIPCHK(c, hipEventRecord(c->ws_free, stream));
+  return BTRAPZ_OK;
+}
+
+BTRAPZ_EXPORT int btrapz_traj_cost_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index, int B,
+                                       int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                       const double *ctrl, const int *status, int N, const double *s_ref, const double *l_ref,
+                                       int ref_stride, double *a_cost, int *n_points, void *stream) {
+  return traj_cost_common(c, false, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
+                          ref_stride, a_cost, n_points, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+BTRAPZ_EXPORT int btrapz_traj_cost_vjp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index, int B,
+                                           int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                           const double *ctrl, const int *status, int N, const double *s_ref,
+                                           const double *l_ref, int ref_stride, const double *a_cost_bar, double *ctrl_bar,
+                                           double *init_bar, double *params_bar, double *s_ref_bar, double *l_ref_bar,
+                                           void *stream) {
+  return traj_cost_common(c, true, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
+                          ref_stride, nullptr, nullptr, a_cost_bar, ctrl_bar, init_bar, params_bar, s_ref_bar, l_ref_bar,
+                          stream);
+}
+
 BTRAPZ_EXPORT int btrapz_rescue_violations_device(btrapz_ctx *c, int B, double *viol, void *stream_) {
   if (!c) return BTRAPZ_EINVAL;
   if (B < 1 || !viol) { c->err = "invalid argument"; return BTRAPZ_EINVAL; }

@@ -1,6 +1,8 @@
 """The batched solve as a differentiable layer: spectral_amd.diff.solve(...) returns (ctrl, cost, status) with a
 torch.autograd graph whose backward is one btrapz_solve_vjp_device launch (include/btrapz_hip.h).  The gradient math
-is HIP; torch only sums the per-candidate parameter gradients of a set."""
+is HIP; torch only sums the per-candidate parameter gradients of a set.  spectral_amd.diff.traj_cost(...) scores the
+sampled trajectories as find_traj does (a_cost, btrapz_traj_cost_device) with a backward of one
+btrapz_traj_cost_vjp_device launch: diff.solve followed by diff.traj_cost is the reference's tuning objective."""
 import types
 
 import torch
@@ -97,3 +99,64 @@ def solve(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, set_
     if params.shape[-1] != N_PARAMS:
         raise ValueError("params rows have %d entries (layout.Shared.as_array() without delta)" % N_PARAMS)
     return _Solve.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, set_index, variant, delta)
+
+
+def _sum_rows(g, set_index, n_sets):
+    """Per-candidate parameter rows [B, 20] -> [n_sets, 20] (candidates outside [0, n_sets) carry zero rows)."""
+    if set_index is None:
+        return g.sum(0)
+    idx = set_index.long().clamp(0, n_sets - 1)
+    out = torch.zeros((n_sets, N_PARAMS), dtype=torch.float64, device=g.device)
+    out.index_add_(0, idx, g)
+    return out
+
+
+class _TrajCost(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctrl, init, params, s_ref, l_ref, seg, solver, seg_count, set_index, status, variant, delta):
+        d = solver.device
+        ctrl_d, init_d, seg_d = (_f64(t.detach()).to(d) for t in (ctrl, init, seg))
+        s_d, l_d = (_f64(t.detach()).to(d) for t in (s_ref, l_ref))
+        B, S = seg_d.shape[1], seg_d.shape[2]
+        rows = params.detach().to("cpu", torch.float64).reshape(-1, N_PARAMS).tolist()
+        sets = [shared_from_params(r, variant, delta) for r in rows]
+        rec = dict(B=B, seg_stride=S, seg=seg_d, seg_count=seg_count, init=init_d)
+        cost, _ = solver.traj_cost(rec, sets, ctrl_d, s_d, l_d, status=status, set_index=set_index)
+        ctx.solver, ctx.sets, ctx.rec, ctx.set_index, ctx.status = solver, sets, rec, set_index, status
+        ctx.arrays = (ctrl_d, s_d, l_d)
+        ctx.shapes = (params.shape, params.device, s_ref.shape, l_ref.shape)
+        return cost
+
+    @staticmethod
+    def backward(ctx, cost_bar):
+        if cost_bar is None:
+            return (None,) * 12
+        ctrl_d, s_d, l_d = ctx.arrays
+        B = ctx.rec["B"]
+        # a candidate that is not scored has cost +inf and a zero gradient: its cotangent must not turn that into NaN
+        g = ctx.solver.traj_cost_vjp(ctx.rec, ctx.sets, ctrl_d, s_d, l_d, cost_bar.reshape(B), status=ctx.status,
+                                     set_index=ctx.set_index)
+        need = ctx.needs_input_grad
+        p_shape, p_dev, s_shape, l_shape = ctx.shapes
+        gp = _sum_rows(g["params"], ctx.set_index, len(ctx.sets)).reshape(p_shape).to(p_dev) if need[2] else None
+        gs = (g["s_ref"].sum(0) if s_d.dim() == 1 else g["s_ref"]).reshape(s_shape) if need[3] else None
+        gl = (g["l_ref"].sum(0) if l_d.dim() == 1 else g["l_ref"]).reshape(l_shape) if need[4] else None
+        return (g["ctrl"] if need[0] else None, g["init"] if need[1] else None, gp, gs, gl,
+                None, None, None, None, None, None, None)
+
+
+def traj_cost(ctrl, seg, init, s_ref, l_ref, params, solver, seg_count=None, set_index=None, status=None, variant=0,
+              delta=0.1):
+    """Differentiable a_cost (btrapz_traj_cost_device): the score find_traj returns, of every candidate's sampled
+    trajectory.  ctrl [B, 12 S], seg [NUM_SEG_FIELDS, B, S] (its durations place the samples), init [B, 6]; s_ref /
+    l_ref: [B, N], or [N] for one line shared by every candidate; params: the SCORING parameter rows, [20] (one set) or
+    [n_sets, 20] with set_index (int32 [B]) -- the cuboid variant uses no weights.  seg_count: int32 [B] for a ragged
+    batch; status: int32 [B] (e.g. the solve's): candidates outside {1, 2} are not scored.  Returns a_cost [B] (+inf where
+    not scored).  Gradients flow to ctrl, init, params (summed over a set's rows), s_ref and l_ref; the durations are not
+    differentiated.  When the same params tensor also feeds diff.solve, autograd adds the explicit part and the part
+    through the solve."""
+    if set_index is None and params.dim() != 1:
+        raise ValueError("params must be [20] without set_index, [n_sets, 20] with it")
+    if params.shape[-1] != N_PARAMS:
+        raise ValueError("params rows have %d entries (layout.Shared.as_array() without delta)" % N_PARAMS)
+    return _TrajCost.apply(ctrl, init, params, s_ref, l_ref, seg, solver, seg_count, set_index, status, variant, delta)

@@ -127,7 +127,8 @@ EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "bt
            "btrapz_device_count", "btrapz_solve_batch_device", "btrapz_argmin_device",
            "btrapz_sample_device", "btrapz_solve_batch_host", "btrapz_solve_ragged_device",
            "btrapz_corridor_batch_device", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
-           "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_eval_states_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
+           "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_traj_cost_device", "btrapz_traj_cost_vjp_device",
+           "btrapz_eval_states_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
            "btrapz_prism_corridor_batch_device",
            "btrapz_find_traj_last_iterations", "btrapz_argmin_pairs_device", "btrapz_options_init",
            "btrapz_rescue_violations_device", "btrapz_find_traj_last_status", "btrapz_debug_mqm_tables",
@@ -228,6 +229,10 @@ def lib():
                                                C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
         l.btrapz_solve_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, dp,
                                               dp, dp, ip, dp, dp, C.POINTER(CGrads), vp]
+        l.btrapz_traj_cost_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, ip,
+                                              C.c_int, dp, dp, C.c_int, dp, ip, vp]
+        l.btrapz_traj_cost_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, ip,
+                                                  C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, dp, vp]
         l.btrapz_eval_states_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, vp]
         l.btrapz_prism_bounds_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, ip, vp]
         l.btrapz_prism_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int,
@@ -477,6 +482,29 @@ class Context:
                                                   ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
                                                   ptr(lam), ptr(status), ptr(ctrl_bar), ptr(cost_bar), C.byref(grads),
                                                   C.c_void_p(stream or 0)), "btrapz_solve_vjp_device")
+
+    def traj_cost_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
+                         ref_stride, a_cost, n_points=None, stream=None):
+        """btrapz_traj_cost_device: a_cost [B] of the sampled trajectories of ctrl, scored with sets (list of layout.Shared;
+        set_index None = every candidate with sets[0]); seg_count / status / n_points may be None; ref_stride N or 0."""
+        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_traj_cost_device(self._h, arr, len(sets), ptr(set_index), int(B), int(seg_stride), ptr(seg),
+                                                  ptr(seg_count), ptr(init), ptr(ctrl), ptr(status), int(N), ptr(s_ref),
+                                                  ptr(l_ref), int(ref_stride), ptr(a_cost), ptr(n_points),
+                                                  C.c_void_p(stream or 0)), "btrapz_traj_cost_device")
+
+    def traj_cost_vjp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
+                             ref_stride, a_cost_bar, ctrl_bar=None, init_bar=None, params_bar=None, s_ref_bar=None,
+                             l_ref_bar=None, stream=None):
+        """btrapz_traj_cost_vjp_device: the gradient device tensors (any may be None) are overwritten."""
+        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_traj_cost_vjp_device(self._h, arr, len(sets), ptr(set_index), int(B), int(seg_stride),
+                                                      ptr(seg), ptr(seg_count), ptr(init), ptr(ctrl), ptr(status), int(N),
+                                                      ptr(s_ref), ptr(l_ref), int(ref_stride), ptr(a_cost_bar),
+                                                      ptr(ctrl_bar), ptr(init_bar), ptr(params_bar), ptr(s_ref_bar),
+                                                      ptr(l_ref_bar), C.c_void_p(stream or 0)), "btrapz_traj_cost_vjp_device")
 
     def workspace_bytes(self):
         """btrapz_workspace_bytes: device memory the context holds for its launches right now."""

@@ -257,6 +257,58 @@ class BatchSolver:
                                   g_ref_end=g["ref_end"], g_dl_bounds=g["dl_bounds"], g_shared=g["shared"], stream=stream)
         return g
 
+    def _cost_args(self, rec, shared_or_sets, ctrl, s_ref, l_ref, status, set_index):
+        if isinstance(rec, dict):
+            B, S, seg_count, seg, init = rec["B"], rec["seg_stride"], rec["seg_count"], rec["seg"], rec["init"]
+        else:
+            B, S, seg_count, seg, init = rec.B, rec.S, None, rec.seg, rec.init
+        sets = list(shared_or_sets) if isinstance(shared_or_sets, (list, tuple)) else [shared_or_sets]
+        d = self.device
+        f = lambda t: t.to(d, dtype=torch.float64).contiguous()
+        t = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+        s_ref, l_ref = f(t(s_ref)), f(t(l_ref))
+        if s_ref.shape != l_ref.shape or s_ref.dim() not in (1, 2) or (s_ref.dim() == 2 and s_ref.shape[0] != B):
+            raise ValueError("s_ref / l_ref: [N] (one line for every candidate) or [B, N]")
+        N = s_ref.shape[-1]
+        if set_index is not None:
+            assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
+        if status is not None:
+            assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B
+        ctrl = f(ctrl)
+        assert tuple(ctrl.shape) == (B, 12 * S), ctrl.shape
+        return dict(B=B, seg_stride=S, sets=sets, set_index=set_index, seg=seg, seg_count=seg_count, init=init, ctrl=ctrl,
+                    status=status, N=N, s_ref=s_ref, l_ref=l_ref, ref_stride=N if s_ref.dim() == 2 else 0)
+
+    def traj_cost(self, rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, status=None, set_index=None):
+        """a_cost -- the score find_traj returns -- of every candidate's sampled trajectory (btrapz_traj_cost_device).
+        rec_or_dbatch: a DeviceBatch or a ragged record; shared_or_sets: the scoring layout.Shared, or a list of sets with
+        set_index (int32 device tensor [B]); ctrl [B, 12 S]; s_ref / l_ref: [B, N] or [N] (one line for all); status
+        (int32 [B], e.g. the solve's): candidates outside {1, 2} are not scored.  Returns (a_cost [B], n_points [B]) device
+        tensors; a candidate that is not scored has +inf and 0."""
+        a = self._cost_args(rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, status, set_index)
+        cost = torch.empty(a["B"], dtype=torch.float64, device=self.device)
+        npts = torch.empty(a["B"], dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.ctx.traj_cost_device(**a, a_cost=cost, n_points=npts, stream=stream)
+        return cost, npts
+
+    def traj_cost_vjp(self, rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, a_cost_bar, status=None, set_index=None):
+        """Gradients of traj_cost (btrapz_traj_cost_vjp_device) for the cotangent a_cost_bar [B].  Returns a dict of device
+        tensors: "ctrl" [B, 12 S], "init" [B, 6], "params" [B, 20] per candidate (layout.Shared.as_array order, without
+        delta), "s_ref" / "l_ref" [B, N] per candidate (also for a shared line: sum the rows)."""
+        a = self._cost_args(rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, status, set_index)
+        B, S, N, d = a["B"], a["seg_stride"], a["N"], self.device
+        abar = torch.as_tensor(a_cost_bar).to(d, dtype=torch.float64).reshape(B).contiguous()
+        g = dict(ctrl=torch.empty((B, 12 * S), dtype=torch.float64, device=d),
+                 init=torch.empty((B, 6), dtype=torch.float64, device=d),
+                 params=torch.empty((B, 20), dtype=torch.float64, device=d),
+                 s_ref=torch.empty((B, N), dtype=torch.float64, device=d),
+                 l_ref=torch.empty((B, N), dtype=torch.float64, device=d))
+        stream = torch.cuda.current_stream(d).cuda_stream
+        self.ctx.traj_cost_vjp_device(**a, a_cost_bar=abar, ctrl_bar=g["ctrl"], init_bar=g["init"], params_bar=g["params"],
+                                      s_ref_bar=g["s_ref"], l_ref_bar=g["l_ref"], stream=stream)
+        return g
+
     def argmin(self, cost, group=None, index_base=0):
         """Arg-min of cost over contiguous groups (default: the whole batch). Device tensors."""
         B = cost.numel()

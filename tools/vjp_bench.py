@@ -68,14 +68,15 @@ def measure(variant, reps, warmup):
     return res
 
 
-def kernel_stats(reps):
-    """Kernel times from rocprofv3 --kernel-trace --stats over a short run of this script (a child process)."""
+def kernel_stats(reps, script=None, args=()):
+    """Kernel times from rocprofv3 --kernel-trace --stats over a short run of `script` (default: this one) with --child
+    (a child process)."""
     exe = shutil.which("rocprofv3")
     if not exe:
         return {"error": "rocprofv3 not found"}
     out = tempfile.mkdtemp(prefix="vjp_prof_")
-    cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "vjp", "--", sys.executable, os.path.abspath(__file__),
-           "--child", "--reps", str(reps), "--warmup", "2"]
+    cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "vjp", "--", sys.executable, os.path.abspath(script or __file__),
+           "--child", "--reps", str(reps), "--warmup", "2", *args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     if r.returncode != 0:
         return {"error": "rocprofv3 exit %d" % r.returncode, "tail": r.stderr[-2000:]}
