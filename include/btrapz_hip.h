@@ -623,6 +623,47 @@ int btrapz_eval_states_device(btrapz_ctx *ctx, int B, int seg_stride, const int 
                               const double *seg, const double *ctrl, int n_times, const double *times,
                               double *x, void *stream);
 
+/* ---- gradients of sampled trajectories and of evaluated states --------------------------------------------------------
+ * Both maps are linear in the control points; the durations (field 0 of seg, and hence the sample counts and the
+ * segment a time falls in) are not differentiated, as everywhere else in the library.  Asynchronous and stream-ordered; no
+ * host round trip; DEVICE pointers; outputs are overwritten; any output may be NULL (not wanted).  Gather kernels without
+ * atomics: repeated calls give bit-identical results.
+ *
+ * Vector-Jacobian product of btrapz_sample_ragged_device (and so of btrapz_sample_device: seg_count NULL means a uniform
+ * batch of seg_stride segments).  B, seg_stride, seg_count, delta, seg, nsel, sel, max_points: as the forward takes them;
+ * out_bar [nsel][6][max_points]: the cotangent of the forward's out.
+ *   ctrl_bar [nsel][12 seg_stride]  ONE ROW PER SELECTION, not per candidate: sel may name a candidate twice, and the
+ *                                   caller sums the rows (no atomics).  A row has the forward's layout: s axis at
+ *                                   [0, 6 S_b), l axis at [6 S_b, 12 S_b); slots beyond 12 S_b are 0
+ *   init_bar [nsel][6]              per selection as well
+ * Defined cases, mirroring the forward: sample 0 is init, so out_bar[:, :, 0] goes to init_bar and nowhere else; samples at
+ * index >= max_points were not written, so their cotangent is ignored; entries of out_bar at and beyond the forward's
+ * npoints are ignored (no written sample lies there: npoints is at least 1 + the sum of (int)(t_k / delta)); a selection
+ * the forward answers with npoints = 0 (index outside [0, B), segment count outside 1..seg_stride) gets zeros in both
+ * outputs; a segment whose duration is not > 0 (outside the forward's domain: find_traj refuses such a corridor) counts as
+ * having no samples.
+ * Refused (BTRAPZ_EINVAL, btrapz_last_error says why): seg, sel or out_bar NULL; B, nsel, max_points or seg_stride < 1;
+ * delta not > 0; seg_stride > BTRAPZ_MAX_SEGMENTS_LONG; ctrl_bar and init_bar both NULL. */
+int btrapz_sample_vjp_device(btrapz_ctx *ctx, int B, int seg_stride, const int *seg_count, double delta,
+                             const double *seg, int nsel, const long long *sel, int max_points,
+                             const double *out_bar, double *ctrl_bar, double *init_bar, void *stream);
+/* Vector-Jacobian product of btrapz_eval_states_device.  B, seg_stride, seg_count, seg, ctrl, n_times, times: as the
+ * forward takes them; x_bar [B][2][n_times][3]: the cotangent of x.
+ *   ctrl_bar  [B][12 seg_stride]  the forward's layout; slots beyond 12 S_b are 0
+ *   times_bar [B][n_times]        the derivative ALONG the trajectory, summed over both axes against x_bar: dp/dt = v,
+ *                                 dv/dt = a, da/dt = the segment's jerk (third Bezier derivative over the squared
+ *                                 duration).  It reads ctrl; ctrl may be NULL when times_bar is NULL.
+ * Defined cases follow the forward's branches: a time that is not > 0 is evaluated at the start of the first segment and
+ * has times_bar = 0; beyond the horizon the forward extrapolates the end state at constant velocity, so p depends on the
+ * last segment's end point and end velocity, v on the end velocity, a is the constant 0, and times_bar = v . p_bar; a time
+ * exactly on a joint belongs to the segment the forward's walk (rem > t_k) leaves it in, and gets that branch's
+ * derivative; a candidate with a segment count outside 1..seg_stride (the forward writes NaN) gets zeros.
+ * Refused (BTRAPZ_EINVAL, btrapz_last_error says why): seg, times or x_bar NULL; B, n_times or seg_stride < 1;
+ * seg_stride > BTRAPZ_MAX_SEGMENTS_LONG; ctrl_bar and times_bar both NULL; times_bar wanted with ctrl NULL. */
+int btrapz_eval_states_vjp_device(btrapz_ctx *ctx, int B, int seg_stride, const int *seg_count,
+                                  const double *seg, const double *ctrl, int n_times, const double *times,
+                                  const double *x_bar, double *ctrl_bar, double *times_bar, void *stream);
+
 /* Test hook: the batch-invariant M' pQp_d M table (solve_3d.cc:87-143) from the library's host builder (find_traj's
  * single launch) and from its device builder (the batched entry points): [2][4][21] doubles each, host pointers. */
 int btrapz_debug_mqm_tables(btrapz_ctx *ctx, const btrapz_shared *shared, double *host_table, double *device_table);

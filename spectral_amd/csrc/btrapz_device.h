@@ -116,6 +116,35 @@ struct AcostArgs {
 __global__ void acost_kernel(const AcostArgs a);
 __global__ void acost_vjp_kernel(const AcostArgs a);
 
+// btrapz_sample_vjp_device / btrapz_eval_states_vjp_device (btrapz_states.hip): one wavefront per selection / candidate,
+// kStatesWaves wavefronts per workgroup
+constexpr int kStatesWaves = 4;
+struct SampleVjpArgs {
+  int B, seg_stride;
+  const int *seg_count;     // [B] or null (uniform)
+  double delta;
+  const double *seg;
+  int nsel;
+  const long long *sel;     // [nsel]
+  int max_points;
+  const double *out_bar;    // [nsel][6][max_points]
+  double *ctrl_bar;         // [nsel][12 seg_stride] or null
+  double *init_bar;         // [nsel][6] or null
+};
+__global__ void sample_vjp_kernel(const SampleVjpArgs a);
+struct StatesVjpArgs {
+  int B, seg_stride;
+  const int *seg_count;     // [B] or null (uniform)
+  const double *seg;
+  const double *ctrl;       // may be null when times_bar is
+  int n_times;
+  const double *times;      // [B][n_times]
+  const double *x_bar;      // [B][2][n_times][3]
+  double *ctrl_bar;         // [B][12 seg_stride] or null
+  double *times_bar;        // [B][n_times] or null
+};
+__global__ void eval_states_vjp_kernel(const StatesVjpArgs a);
+
 struct PrismRoad {              // btrapz_road in the form the prism stage uses it (prism_core.h)
   double rate;                  // knots per second (the reference hard-codes 10: `i/10`, `t0*10`)
   double s_lo, s_hi, l_lo, l_hi, l_safe, w_safe;

@@ -1134,6 +1134,76 @@ BTRAPZ_EXPORT int btrapz_traj_cost_vjp_device(btrapz_ctx *c, const btrapz_shared
                           stream);
 }
 
+// Vector-Jacobian products of the sampling and of the state evaluation (btrapz_states.hip): one wavefront per selection /
+// candidate, kStatesWaves of them per workgroup.  They read no workspace of the context.
+BTRAPZ_EXPORT int btrapz_sample_vjp_device(btrapz_ctx *c, int B, int seg_stride, const int *seg_count, double delta,
+                                        const double *seg, int nsel, const long long *sel, int max_points,
+                                        const double *out_bar, double *ctrl_bar, double *init_bar, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (!seg || !sel || !out_bar) {
+    c->err = "invalid argument: seg, sel and out_bar must be non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (B < 1 || nsel < 1 || max_points < 1 || seg_stride < 1) {
+    c->err = "invalid argument: B >= 1, nsel >= 1, max_points >= 1 and seg_stride >= 1";
+    return BTRAPZ_EINVAL;
+  }
+  if (!(delta > 0)) {
+    c->err = "invalid argument: delta must be > 0";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: seg_stride > BTRAPZ_MAX_SEGMENTS_LONG";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl_bar && !init_bar) {
+    c->err = "invalid argument: ctrl_bar and init_bar are both null";
+    return BTRAPZ_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  SampleVjpArgs a;
+  a.B = B; a.seg_stride = seg_stride; a.seg_count = seg_count; a.delta = delta; a.seg = seg;
+  a.nsel = nsel; a.sel = sel; a.max_points = max_points; a.out_bar = out_bar; a.ctrl_bar = ctrl_bar; a.init_bar = init_bar;
+  const unsigned blocks = (unsigned)(((size_t)nsel + kStatesWaves - 1) / kStatesWaves);
+  hipLaunchKernelGGL(sample_vjp_kernel, dim3(blocks), dim3(64 * kStatesWaves), 0, (hipStream_t)stream_, a);
+  HIPCHK(c, hipGetLastError());
+  return BTRAPZ_OK;
+}
+
+BTRAPZ_EXPORT int btrapz_eval_states_vjp_device(btrapz_ctx *c, int B, int seg_stride, const int *seg_count, const double *seg,
+                                             const double *ctrl, int n_times, const double *times, const double *x_bar,
+                                             double *ctrl_bar, double *times_bar, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (!seg || !times || !x_bar) {
+    c->err = "invalid argument: seg, times and x_bar must be non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (B < 1 || n_times < 1 || seg_stride < 1) {
+    c->err = "invalid argument: B >= 1, n_times >= 1 and seg_stride >= 1";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: seg_stride > BTRAPZ_MAX_SEGMENTS_LONG";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl_bar && !times_bar) {
+    c->err = "invalid argument: ctrl_bar and times_bar are both null";
+    return BTRAPZ_EINVAL;
+  }
+  if (times_bar && !ctrl) {
+    c->err = "invalid argument: times_bar needs ctrl";
+    return BTRAPZ_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  StatesVjpArgs a;
+  a.B = B; a.seg_stride = seg_stride; a.seg_count = seg_count; a.seg = seg; a.ctrl = ctrl;
+  a.n_times = n_times; a.times = times; a.x_bar = x_bar; a.ctrl_bar = ctrl_bar; a.times_bar = times_bar;
+  const unsigned blocks = (unsigned)(((size_t)B + kStatesWaves - 1) / kStatesWaves);
+  hipLaunchKernelGGL(eval_states_vjp_kernel, dim3(blocks), dim3(64 * kStatesWaves), 0, (hipStream_t)stream_, a);
+  HIPCHK(c, hipGetLastError());
+  return BTRAPZ_OK;
+}
+
 BTRAPZ_EXPORT int btrapz_rescue_violations_device(btrapz_ctx *c, int B, double *viol, void *stream_) {
   if (!c) return BTRAPZ_EINVAL;
   if (B < 1 || !viol) { c->err = "invalid argument"; return BTRAPZ_EINVAL; }

@@ -160,3 +160,102 @@ def traj_cost(ctrl, seg, init, s_ref, l_ref, params, solver, seg_count=None, set
     if params.shape[-1] != N_PARAMS:
         raise ValueError("params rows have %d entries (layout.Shared.as_array() without delta)" % N_PARAMS)
     return _TrajCost.apply(ctrl, init, params, s_ref, l_ref, seg, solver, seg_count, set_index, status, variant, delta)
+
+
+def _sum_selections(rows, sel, B):
+    """Per-selection rows [nsel, n] -> per-candidate rows [B, n] in a fixed order (sel may repeat a candidate, and
+    index_add_ on the device adds with atomics): the r-th selection of every candidate is added in pass r, and within a
+    pass no candidate appears twice.  Selections outside [0, B) carry zero rows."""
+    out = torch.zeros((B, rows.shape[1]), dtype=rows.dtype, device=rows.device)
+    idx = sel.long().clamp(0, B - 1)
+    order = torch.sort(idx, stable=True).indices
+    srt = idx[order]
+    pos = torch.arange(srt.numel(), device=srt.device)
+    heads = torch.ones_like(srt, dtype=torch.bool)
+    heads[1:] = srt[1:] != srt[:-1]
+    rank = torch.empty_like(pos)
+    rank[order] = pos - torch.cummax(torch.where(heads, pos, torch.zeros_like(pos)), 0).values
+    for r in range(int(rank.max().item()) + 1):
+        m = rank == r
+        out[idx[m]] += rows[m]
+    return out
+
+
+class _Sample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctrl, init, seg, solver, seg_count, sel, delta):
+        d = solver.device
+        ctrl_d, init_d, seg_d = (_f64(t.detach()).to(d) for t in (ctrl, init, seg))
+        B, S = seg_d.shape[1], seg_d.shape[2]
+        sel = (torch.arange(B, device=d) if sel is None else sel).to(d, dtype=torch.int64).contiguous()
+        if seg_count is None:
+            out, npts = solver.sample(types.SimpleNamespace(B=B, S=S, seg=seg_d, init=init_d), ctrl_d, sel, delta)
+        else:
+            t = seg_d[L.F_T] * (torch.arange(S, device=d)[None, :] < seg_count[:, None])
+            max_points = int(torch.floor(t / delta + 1e-9).sum(1).max().item()) + 2
+            out = torch.zeros((sel.numel(), 6, max_points), dtype=torch.float64, device=d)
+            npts = torch.zeros(sel.numel(), dtype=torch.int32, device=d)
+            solver.ctx.sample_ragged_device(B, S, seg_count, delta, seg_d, init_d, ctrl_d, sel, max_points, out, npts,
+                                            stream=torch.cuda.current_stream(d).cuda_stream)
+        ctx.solver, ctx.sel, ctx.delta = solver, sel, delta
+        ctx.rec = dict(B=B, seg_stride=S, seg=seg_d, seg_count=seg_count)
+        ctx.mark_non_differentiable(npts)
+        return out, npts
+
+    @staticmethod
+    def backward(ctx, out_bar, _npts_bar):
+        if out_bar is None:
+            return (None,) * 7
+        need = ctx.needs_input_grad
+        g = ctx.solver.sample_vjp(ctx.rec, ctx.sel, ctx.delta, out_bar, want_ctrl=need[0], want_init=need[1])
+        B = ctx.rec["B"]
+        return (_sum_selections(g["ctrl"], ctx.sel, B) if need[0] else None,
+                _sum_selections(g["init"], ctx.sel, B) if need[1] else None, None, None, None, None, None)
+
+
+def sample(ctrl, seg, init, solver, seg_count=None, sel=None, delta=0.1):
+    """Differentiable Bernstein sampling (btrapz_sample_device / btrapz_sample_ragged_device): the rows find_traj writes.
+    ctrl [B, 12 S], seg [NUM_SEG_FIELDS, B, S] (its durations place the samples), init [B, 6] (sample 0); seg_count: int32
+    [B] for a ragged batch; sel: the candidates to sample (int64, default every candidate in order; may repeat).  Returns
+    (traj [nsel, 6, max_points] -- s, ds, dds, l, dl, ddl every delta seconds -- and npoints [nsel], not
+    differentiable).  Gradients flow to ctrl and init through one btrapz_sample_vjp_device launch, whose per-selection
+    rows are summed onto the candidates in a fixed order; the durations are not differentiated."""
+    return _Sample.apply(ctrl, init, seg, solver, seg_count, sel, delta)
+
+
+class _EvalStates(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctrl, times, seg, solver, seg_count):
+        d = solver.device
+        ctrl_d, times_d, seg_d = (_f64(t.detach()).to(d) for t in (ctrl, times, seg))
+        B, S = seg_d.shape[1], seg_d.shape[2]
+        if seg_count is None:
+            x = solver.eval_states(types.SimpleNamespace(B=B, S=S, seg=seg_d), ctrl_d, times_d)
+        else:
+            n = times_d.shape[1]
+            x = torch.empty((B, 2, n, 3), dtype=torch.float64, device=d)
+            solver.ctx.eval_states_device(B, S, seg_count, seg_d, ctrl_d, n, times_d, x,
+                                          stream=torch.cuda.current_stream(d).cuda_stream)
+        ctx.solver = solver
+        ctx.rec = dict(B=B, seg_stride=S, seg=seg_d, seg_count=seg_count)
+        ctx.arrays = (ctrl_d, times_d)
+        ctx.times_shape = times.shape
+        return x
+
+    @staticmethod
+    def backward(ctx, x_bar):
+        if x_bar is None:
+            return (None,) * 5
+        need = ctx.needs_input_grad
+        ctrl_d, times_d = ctx.arrays
+        g = ctx.solver.eval_states_vjp(ctx.rec, ctrl_d, times_d, x_bar, want_ctrl=need[0], want_times=need[1])
+        return (g["ctrl"] if need[0] else None, g["times"].reshape(ctx.times_shape) if need[1] else None, None, None, None)
+
+
+def eval_states(ctrl, seg, times, solver, seg_count=None):
+    """Differentiable state evaluation (btrapz_eval_states_device): x [B, 2, n_times, 3] = (p, v, a) per axis of every
+    candidate at times [B, n_times] seconds from the start of its horizon.  ctrl [B, 12 S], seg [NUM_SEG_FIELDS, B, S];
+    seg_count: int32 [B] for a ragged batch.  Gradients flow to ctrl and to times (the derivative along the trajectory:
+    0 for a time that is not > 0, the end velocity beyond the horizon) through one btrapz_eval_states_vjp_device launch;
+    the durations are not differentiated."""
+    return _EvalStates.apply(ctrl, times, seg, solver, seg_count)

@@ -128,7 +128,7 @@ EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "bt
            "btrapz_sample_device", "btrapz_solve_batch_host", "btrapz_solve_ragged_device",
            "btrapz_corridor_batch_device", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
            "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_traj_cost_device", "btrapz_traj_cost_vjp_device",
-           "btrapz_eval_states_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
+           "btrapz_eval_states_device", "btrapz_sample_vjp_device", "btrapz_eval_states_vjp_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
            "btrapz_prism_corridor_batch_device",
            "btrapz_find_traj_last_iterations", "btrapz_argmin_pairs_device", "btrapz_options_init",
            "btrapz_rescue_violations_device", "btrapz_find_traj_last_status", "btrapz_debug_mqm_tables",
@@ -234,6 +234,8 @@ def lib():
         l.btrapz_traj_cost_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, ip,
                                                   C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, dp, vp]
         l.btrapz_eval_states_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, vp]
+        l.btrapz_sample_vjp_device.argtypes = [vp, C.c_int, C.c_int, ip, C.c_double, dp, C.c_int, llp, C.c_int, dp, dp, dp, vp]
+        l.btrapz_eval_states_vjp_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, dp, dp, vp]
         l.btrapz_prism_bounds_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, ip, vp]
         l.btrapz_prism_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int,
                                                          C.c_double, dp, dp, dp, dp, C.c_int, dp, ip, dp, dp, ip, vp]
@@ -545,6 +547,25 @@ class Context:
         self._check(lib().btrapz_eval_states_device(self._h, B, seg_stride, ptr(seg_count), ptr(seg), ptr(ctrl),
                                                     int(n_times), ptr(times), ptr(x), C.c_void_p(stream or 0)),
                     "btrapz_eval_states_device")
+
+    def eval_states_vjp_device(self, B, seg_stride, seg_count, seg, ctrl, n_times, times, x_bar, ctrl_bar=None,
+                               times_bar=None, stream=None):
+        """btrapz_eval_states_vjp_device: ctrl_bar [B, 12 seg_stride] and times_bar [B, n_times] (either may be None) are
+        overwritten; ctrl may be None when times_bar is."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_eval_states_vjp_device(self._h, int(B), int(seg_stride), ptr(seg_count), ptr(seg), ptr(ctrl),
+                                                        int(n_times), ptr(times), ptr(x_bar), ptr(ctrl_bar), ptr(times_bar),
+                                                        C.c_void_p(stream or 0)), "btrapz_eval_states_vjp_device")
+
+    def sample_vjp_device(self, B, seg_stride, seg_count, delta, seg, sel, max_points, out_bar, ctrl_bar=None, init_bar=None,
+                          stream=None, nsel=None):
+        """btrapz_sample_vjp_device: ctrl_bar [nsel, 12 seg_stride] and init_bar [nsel, 6], one row per SELECTION (either
+        may be None), are overwritten.  nsel: the length of sel unless given."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_sample_vjp_device(self._h, int(B), int(seg_stride), ptr(seg_count), float(delta), ptr(seg),
+                                                   int(nsel if nsel is not None else sel.numel() if sel is not None else 0), ptr(sel), int(max_points),
+                                                   ptr(out_bar), ptr(ctrl_bar), ptr(init_bar), C.c_void_p(stream or 0)),
+                    "btrapz_sample_vjp_device")
 
     def corridor_batch_device(self, variant, B, N, num_obs, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots,
                               s_ref, l_ref, seg_stride, seg, seg_count, ref_end, dl_bounds, stream=None):

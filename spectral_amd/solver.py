@@ -330,3 +330,46 @@ class BatchSolver:
         self.ctx.sample_device(dbatch.B, dbatch.S, delta, dbatch.seg, dbatch.init, ctrl, sel, max_points, out, npts,
                                stream=stream)
         return out, npts
+
+    def _layout_of(self, rec_or_dbatch):
+        if isinstance(rec_or_dbatch, dict):
+            return rec_or_dbatch["B"], rec_or_dbatch["seg_stride"], rec_or_dbatch.get("seg_count"), rec_or_dbatch["seg"]
+        return rec_or_dbatch.B, rec_or_dbatch.S, None, rec_or_dbatch.seg
+
+    def sample_vjp(self, rec_or_dbatch, sel, delta, out_bar, want_ctrl=True, want_init=True):
+        """Vector-Jacobian product of sample (btrapz_sample_vjp_device).  rec_or_dbatch: the DeviceBatch or ragged record
+        that was sampled; sel: the selection of the forward; out_bar [nsel, 6, max_points]: the cotangent of the samples
+        (max_points is read off its shape).  Returns a dict of device tensors with ONE ROW PER SELECTION -- "ctrl"
+        [nsel, 12 S] and "init" [nsel, 6]; a candidate that sel names twice has two rows, which the caller sums."""
+        B, S, seg_count, seg = self._layout_of(rec_or_dbatch)
+        d = self.device
+        sel = sel.to(d, dtype=torch.int64).contiguous()
+        out_bar = out_bar.to(d, dtype=torch.float64).contiguous()
+        n = sel.numel()
+        if out_bar.dim() != 3 or out_bar.shape[0] != n or out_bar.shape[1] != 6:
+            raise ValueError("out_bar: [nsel, 6, max_points]")
+        g = dict(ctrl=torch.empty((n, 12 * S), dtype=torch.float64, device=d) if want_ctrl else None,
+                 init=torch.empty((n, 6), dtype=torch.float64, device=d) if want_init else None)
+        stream = torch.cuda.current_stream(d).cuda_stream
+        self.ctx.sample_vjp_device(B, S, seg_count, delta, seg, sel, out_bar.shape[2], out_bar, ctrl_bar=g["ctrl"],
+                                   init_bar=g["init"], stream=stream)
+        return g
+
+    def eval_states_vjp(self, rec_or_dbatch, ctrl, times, x_bar, want_ctrl=True, want_times=True):
+        """Vector-Jacobian product of eval_states (btrapz_eval_states_vjp_device).  rec_or_dbatch: a DeviceBatch or a ragged
+        record; ctrl [B, 12 S]; times [B, n_times]; x_bar [B, 2, n_times, 3]: the cotangent of the states.  Returns a dict
+        of device tensors: "ctrl" [B, 12 S] and "times" [B, n_times], the derivative along the trajectory (0 for a time
+        that is not > 0)."""
+        B, S, seg_count, seg = self._layout_of(rec_or_dbatch)
+        d = self.device
+        f = lambda t: t.to(d, dtype=torch.float64).contiguous()
+        times, x_bar, ctrl = f(times), f(x_bar), f(ctrl)
+        n = times.shape[1]
+        if tuple(times.shape) != (B, n) or tuple(x_bar.shape) != (B, 2, n, 3) or tuple(ctrl.shape) != (B, 12 * S):
+            raise ValueError("times [B, n_times], x_bar [B, 2, n_times, 3], ctrl [B, 12 S]")
+        g = dict(ctrl=torch.empty((B, 12 * S), dtype=torch.float64, device=d) if want_ctrl else None,
+                 times=torch.empty((B, n), dtype=torch.float64, device=d) if want_times else None)
+        stream = torch.cuda.current_stream(d).cuda_stream
+        self.ctx.eval_states_vjp_device(B, S, seg_count, seg, ctrl, n, times, x_bar, ctrl_bar=g["ctrl"],
+                                        times_bar=g["times"], stream=stream)
+        return g

@@ -72,3 +72,78 @@ def descend(solver, kb, variant, weights, starts=16, steps=30, seed=0, lr=1.0, s
     best = min(best, float(a[fin].min()))
     return dict(start_mean=means[0], final_mean=means[-1], best=best, means=means, solves=starts * (steps + 1),
                 weights=P.detach()[:, :10].cpu().numpy())
+
+
+ROW_OF_WEIGHT = (2, 3, 6, 7, 0, 1, 4, 5, 8, 9)   # weights.txt / Params position -> position in the parameter row (shared_of)
+
+
+def fit_trajectory(solver, kb, variant, target, weights, starts=16, steps=100, seed=0, lr=0.05, spread=float(np.log(1.3)),
+                   columns=(0, 1, 2, 3, 4, 5)):
+    """Which weights reproduce a recorded trajectory?  Multi-start projected Adam on the ten weights of candidate 0 of the
+    knots.KnotBatch kb, organised as `descend`: every start is a parameter set of one batched launch, the gradient runs
+    through diff.solve + diff.sample.  Minimised per start: the mean squared difference between the sampled trajectory
+    and target [6, n] (rows s, ds, dds, l, dl, ddl every kb.delta seconds, as find_traj writes them) over `columns` (a
+    subset of the six) and the samples both have.  The starts are `weights` (ten values, weights.txt / Params order) with
+    every log-weight moved by +-spread (random signs from `seed`); Adam steps on the
+    log-weights, projected on the box BOX.  A start whose solve fails (status outside {1, 2}) is left out of the means.
+
+    Returns what `descend` returns with the loss in place of a_cost -- the mean loss of the starts at the first and after
+    the last step, the best loss seen, the per-step means, the solve count -- plus "losses" (per start, after the last
+    step), "max_dev" ([6] largest |difference| per column of the best start, over the compared samples) and "weights"
+    [starts, 10] in weights.txt order.
+
+    What the Nelder-Mead fit of tests/golden/fit_weights.py established holds here too: the solve's optimum is invariant
+    under a common factor on one axis' weights, so weights are recoverable only up to one scale per axis; the loss, not
+    the distance to some known weights, is the measure of a fit."""
+    d = solver.device
+    W = np.clip(np.asarray(weights, dtype=np.float64)[:10], *BOX)
+    rec = replicated_record(solver, kb, variant, starts)
+    rng = np.random.default_rng(seed)
+    w0 = W[None, :] * np.exp(spread * rng.choice([-1.0, 1.0], (starts, 10)))
+    rows = np.stack([diff.params_from_shared(shared_of(w, kb.header, kb.delta, variant)) for w in np.clip(w0, *BOX)])
+    U = torch.tensor(np.log(rows[:, :10]), dtype=torch.float64, device=d, requires_grad=True)
+    rest = torch.tensor(rows[:, 10:], dtype=torch.float64, device=d)
+    idx = torch.arange(starts, dtype=torch.int32, device=d)
+    tgt = torch.as_tensor(np.asarray(target, dtype=np.float64), device=d)
+    cols = torch.tensor(sorted(int(c) for c in columns), dtype=torch.long, device=d)
+    lo, hi = float(np.log(BOX[0])), float(np.log(BOX[1]))
+    opt = torch.optim.Adam([U], lr=lr)
+    means, best, state = [], np.inf, {}
+
+    def evaluate():
+        P = torch.cat([torch.exp(U), rest], dim=1)
+        ctrl, _, st = diff.solve(solver, rec["seg"], rec["init"], rec["ref_end"], rec["dl_bounds"], P,
+                                 seg_count=rec["seg_count"], set_index=idx, variant=variant, delta=kb.delta)
+        traj, npts = diff.sample(ctrl, rec["seg"], rec["init"], solver, seg_count=rec["seg_count"], delta=kb.delta)
+        if "n" not in state:
+            state["n"] = min(int(tgt.shape[1]), int(traj.shape[2]), int(npts.min().item()))
+        n = state["n"]
+        dev = traj[:, :, :n] - tgt[None, :, :n]
+        loss = (dev[:, cols] ** 2).mean(dim=(1, 2))
+        ok = (st == 1) | (st == 2)
+        return loss, ok, dev
+
+    def record(loss, ok):
+        nonlocal best
+        l = loss.detach()[ok]
+        means.append(float(l.mean()) if l.numel() else float("nan"))
+        if l.numel():
+            best = min(best, float(l.min()))
+
+    for _ in range(steps):
+        opt.zero_grad()
+        loss, ok, _ = evaluate()
+        record(loss, ok)
+        loss[ok].sum().backward()
+        opt.step()
+        with torch.no_grad():
+            U.clamp_(lo, hi)
+    with torch.no_grad():
+        loss, ok, dev = evaluate()
+    record(loss, ok)
+    final = torch.where(ok, loss, torch.full_like(loss, float("inf")))
+    b = int(torch.argmin(final).item())
+    w_rows = torch.exp(U.detach()).cpu().numpy()
+    return dict(start_mean=means[0], final_mean=means[-1], best=best, means=means, solves=starts * (steps + 1),
+                losses=final.cpu().numpy(), max_dev=dev[b].abs().amax(dim=1).cpu().numpy(), samples=state["n"],
+                weights=w_rows[:, list(ROW_OF_WEIGHT)])
