@@ -573,6 +573,53 @@ int btrapz_solve_vjp_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_se
                             const double *ctrl_bar, const double *cost_bar,
                             const btrapz_grads *out, void *stream);
 
+/* ---- directional derivatives of a solve (Jacobian-vector products) --------------------------------------------------
+ * The forward-mode mirror of btrapz_solve_vjp_device: for T >= 1 input directions per candidate, the derivative of
+ * EVERY output along each of them, in one launch.  At the optimum x = ctrl[b] with the active set A of the solve (the
+ * VJP's rule: a row is active when its multiplier exceeds its slack at x; equalities always) the rows do not depend on
+ * any differentiated input, so
+ *     [ P  A' ] [dx ]   [-(dP x + dq)]
+ *     [ A  0  ] [dmu] = [    db_A    ]      dcost = (P x + q)' dx + x' dP x / 2 + dq' x,
+ * dP, dq, db the assembly applied to the tangents: the partial derivatives the VJP applies transposed.  A tangent of
+ * init moves the particular solution of the eliminated equalities as well.  The matrix is the VJP's, factorised once per
+ * axis problem and reused by all T right-hand sides (method of multipliers, relative penalty 1e6, three passes each).
+ * Inputs: those of btrapz_solve_vjp_device (the solve's inputs, and its outputs ctrl, lam, status; elastic = 0), T, and
+ * the tangents, DEVICE pointers with a leading axis T, any may be NULL (zero):
+ *   seg_dot       [T][NUM_SEG_FIELDS][B][seg_stride]  fields 1-16; field 0 (T) is ignored
+ *   init_dot      [T][B][6]
+ *   ref_end_dot   [T][B][2]                           through q's end term (its d_ref factor kept)
+ *   dl_bounds_dot [T][B][10]
+ *   shared_dot    [T][B][20] PER CANDIDATE, layout.Shared.as_array() order as btrapz_grads.shared; delta and variant are
+ *                            not differentiated
+ * Outputs, overwritten, either may be NULL but not both:
+ *   ctrl_dot [T][B][12 seg_stride]  the forward's layout: s axis at [0, 6 S_b), l axis at [6 S_b, 12 S_b), the slots
+ *                                   beyond 12 S_b written as 0
+ *   cost_dot [T][B]
+ * Defined cases -- exactly the VJP's, read forwards, which makes J here the exact transpose of the VJP's J':
+ *   - a candidate whose status is not 1 or 2, or that was not solved (set_index outside [0, n_sets), a segment count
+ *     outside 1..seg_stride), gets 0 in both outputs for every tangent;
+ *   - the tangent of a bound that is no bound (|v| >= 1e9, moved out by the solve, an acceleration / jerk limit the
+ *     library moved, the s axis acceleration clamped to +-1000) is ignored;
+ *   - the cuboid variant's s axis interval takes the derivative of the branch taken;
+ *   - a joint's position and velocity bound stated by two segments takes the tangent of the field that supplied the
+ *     tighter bound, on an exact tie segment k's.
+ * Refused (BTRAPZ_EINVAL, btrapz_last_error says why): seg_stride > BTRAPZ_MAX_SEGMENTS, ctrl, lam or status NULL, both
+ * outputs NULL, every tangent NULL, T < 1 or T > BTRAPZ_MAX_TANGENTS, sets of different variant or delta.
+ * Asynchronous and stream-ordered, no host round trip; the M'QM tables come from the context's cache. */
+#define BTRAPZ_MAX_TANGENTS 32
+typedef struct btrapz_tangents { /* DEVICE pointers, leading axis T; any may be NULL (zero), not all */
+  const double *seg;       /* [T][NUM_SEG_FIELDS][B][seg_stride] */
+  const double *init;      /* [T][B][6] */
+  const double *ref_end;   /* [T][B][2] */
+  const double *dl_bounds; /* [T][B][10] */
+  const double *shared;    /* [T][B][20] per candidate */
+} btrapz_tangents;
+int btrapz_solve_jvp_device(btrapz_ctx *ctx, const btrapz_shared *sets, int n_sets, const int *set_index,
+                            int B, int seg_stride, const double *seg, const int *seg_count,
+                            const double *init, const double *ref_end, const double *dl_bounds,
+                            const double *ctrl, const double *lam, const int *status,
+                            int T, const btrapz_tangents *tangents, double *ctrl_dot, double *cost_dot, void *stream);
+
 /* ---- trajectory scores (a_cost) and their gradients ------------------------------------------------------------------
  * a_cost[b] is what find_traj returns for a trajectory (trp_wrapper.cpp:207-286 / cub_wrapper.cpp:201-262, restated in
  * traj_cost.h) on the samples btrapz_sample_device produces from ctrl[b]: sample 0 is init[b], samples 1..total the

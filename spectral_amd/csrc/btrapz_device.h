@@ -95,6 +95,22 @@ struct VjpArgs {
 };
 __global__ void vjp_kernel(const VjpArgs a);
 
+// btrapz_solve_jvp_device (btrapz_jvp.hip)
+struct JvpArgs {
+  int B, S, seg_stride, T;  // S as in VjpArgs; T tangents per candidate (1..BTRAPZ_MAX_TANGENTS)
+  const int *seg_count;     // [B] or null
+  const Shared *sets;       // [n_sets] device view of the parameter sets
+  int n_sets;
+  const int *set_index;     // [B] or null (set 0)
+  const double *mqm;        // [n_sets][168] M'QM tables of the sets
+  const double *mqm_unit;   // [168] the same with every weight 1
+  const double *seg, *ref_end, *dl_bounds, *ctrl, *lam;
+  const int *status;
+  const double *seg_dot, *init_dot, *ref_end_dot, *dl_dot, *shared_dot;   // tangents, leading axis T; any may be null (zero)
+  double *ctrl_dot, *cost_dot;                                             // [T][B][12 seg_stride], [T][B]; either may be null
+};
+__global__ void jvp_kernel(const JvpArgs a);
+
 // btrapz_traj_cost_device / btrapz_traj_cost_vjp_device (btrapz_acost.hip)
 struct AcostArgs {
   int B, seg_stride;

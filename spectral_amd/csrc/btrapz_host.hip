@@ -1049,6 +1049,72 @@ BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *se
   return BTRAPZ_OK;
 }
 
+// Directional derivatives of a solve (btrapz_solve_jvp_device): one launch of jvp_kernel (btrapz_jvp.hip), vjp_kernel's
+// groups of S lanes; a workgroup is the two wavefronts (s axis, l axis) of the same candidates.
+BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                       int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                       const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                       const int *status, int T, const btrapz_tangents *tan, double *ctrl_dot,
+                                       double *cost_dot, void *stream_) {
+  (void)init;   // (the tangent system is stated at the returned control points; init_dot is what moves them)
+  if (!c) return BTRAPZ_EINVAL;
+  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds) {
+    c->err = "invalid argument (jvp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays non-null)";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS) {
+    c->err = "invalid argument: jvp of candidates of at most BTRAPZ_MAX_SEGMENTS segments (the long form keeps no multipliers)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl || !lam || !status) {
+    c->err = "invalid argument: jvp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl_dot && !cost_dot) {
+    c->err = "invalid argument: jvp needs ctrl_dot or cost_dot (both NULL)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!tan || (!tan->seg && !tan->init && !tan->ref_end && !tan->dl_bounds && !tan->shared)) {
+    c->err = "invalid argument: jvp needs at least one tangent (all NULL)";
+    return BTRAPZ_EINVAL;
+  }
+  if (T < 1 || T > BTRAPZ_MAX_TANGENTS) {
+    c->err = "invalid argument: jvp of 1 <= T <= BTRAPZ_MAX_TANGENTS tangents per call";
+    return BTRAPZ_EINVAL;
+  }
+  for (int g = 1; g < n_sets; g++)
+    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
+      c->err = "invalid argument: every parameter set must have the same variant and delta";
+      return BTRAPZ_EINVAL;
+    }
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  int rc = sets_tables(c, sets, n_sets, stream);
+  if (rc != BTRAPZ_OK) return rc;
+  if (!c->d_mqm_unit) {   // (as btrapz_solve_vjp_device builds it)
+    HIPCHK(c, hipMalloc(&c->d_mqm_unit, sizeof(double) * 168));
+    MqmWeights ones;
+    for (int ax = 0; ax < 2; ax++)
+      for (int d = 0; d < 4; d++) ones.w[ax][d] = 1.0;
+    hipLaunchKernelGGL(mqm_table_kernel, dim3(1), dim3(192), 0, stream, ones, c->d_mqm_unit);
+    HIPCHK(c, hipGetLastError());
+  }
+  JvpArgs a;
+  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.T = T; a.seg_count = seg_count;
+  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
+  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
+  a.seg_dot = tan->seg; a.init_dot = tan->init; a.ref_end_dot = tan->ref_end; a.dl_dot = tan->dl_bounds; a.shared_dot = tan->shared;
+  a.ctrl_dot = ctrl_dot; a.cost_dot = cost_dot;
+  const unsigned gpw = 64u / (unsigned)seg_stride;
+  const unsigned blocks = (unsigned)(((size_t)B + gpw - 1) / gpw);
+  hipLaunchKernelGGL(jvp_kernel, dim3(blocks), dim3(128), 0, stream, a);
+  HIPCHK(c, hipGetLastError());
+  c->ws_stream = stream; c->ws_used = true;
+  HIPCHK(c, hipEventRecord(c->ws_free, stream));
+  return BTRAPZ_OK;
+}
+
 // a_cost of sampled trajectories and its VJP (btrapz_traj_cost_device, btrapz_traj_cost_vjp_device): one workgroup of 64
 // per candidate (btrapz_acost.hip); the scoring sets come from the context's cache of btrapz_solve_sets_device.
 static int traj_cost_common(btrapz_ctx *c, bool vjp, const btrapz_shared *sets, int n_sets, const int *set_index, int B,

@@ -259,3 +259,103 @@ def eval_states(ctrl, seg, times, solver, seg_count=None):
     0 for a time that is not > 0, the end velocity beyond the horizon) through one btrapz_eval_states_vjp_device launch;
     the durations are not differentiated."""
     return _EvalStates.apply(ctrl, times, seg, solver, seg_count)
+
+
+# ---- forward mode: Jacobian-vector products (btrapz_solve_jvp_device) --------------------------------------------------
+
+def _record(seg, init, ref_end, dl_bounds, seg_count):
+    B, S = seg.shape[1], seg.shape[2]
+    if seg_count is None:
+        return types.SimpleNamespace(B=B, S=S, seg=seg, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
+    return dict(B=B, seg_stride=S, seg=seg, seg_count=seg_count, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
+
+
+def solve_kept(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, set_index=None, variant=0, delta=0.1):
+    """The solve of diff.solve without a graph: multipliers kept, no rescue pass.  Returns the result dict ("ctrl", "cost",
+    "status", "iters", "lam"): what solve_jacobian(out=...) and BatchSolver.solve_jvp / solve_vjp take."""
+    d = solver.device
+    seg, init, ref_end, dl_bounds = (_f64(t.detach()).to(d) for t in (seg, init, ref_end, dl_bounds))
+    B, S = seg.shape[1], seg.shape[2]
+    sets = [shared_from_params(r, variant, delta) for r in params.detach().to("cpu", torch.float64).reshape(-1, N_PARAMS).tolist()]
+    o = dict(ctrl=torch.zeros((B, 12 * S), dtype=torch.float64, device=d), cost=torch.empty(B, dtype=torch.float64, device=d),
+             status=torch.empty(B, dtype=torch.int32, device=d), iters=torch.empty(B, dtype=torch.int32, device=d))
+    rec = _record(seg, init, ref_end, dl_bounds, seg_count)
+    if set_index is not None and seg_count is None:
+        o = solver.solve_sets(rec, sets, set_index, keep_multipliers=True, out=o)
+    elif set_index is not None:
+        o = solver.solve_sets_ragged(rec, sets, set_index, keep_multipliers=True)
+    else:
+        o["lam"] = torch.empty((2, 36, B, S), dtype=torch.float64, device=d)
+        solver.ctx.solve_warm_device(B, S, sets[0], seg, seg_count, init, ref_end, dl_bounds, o["ctrl"], o["cost"],
+                                     o["status"], o["iters"], lam_out=o["lam"], stream=torch.cuda.current_stream(d).cuda_stream)
+    return o
+
+
+def solve_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, *, seg_count=None, set_index=None, variant=0,
+                   delta=0.1, log=False, out=None):
+    """Columns of the solve's Jacobian with respect to its parameters: one solve with the multipliers kept (solve_kept)
+    and ONE btrapz_solve_jvp_device launch with
+    T = len(columns) unit tangents on the named columns of the parameter row (shared_from_params' order), each
+    candidate's on its own set's row.  log=True: the derivative with respect to the logarithm of the parameter (the unit
+    tangent scaled by the parameter's value).  Arguments as diff.solve.  Returns a dict of device tensors: "ctrl"
+    [B, 12 S], "cost" [B], "status" [B], "dctrl" [T, B, 12 S], "dcost" [T, B], and "out", the solve's result dict.
+
+    out: the result dict of a solve_kept of a previous call, to skip the solve (the fit differentiates the point its last
+    step accepted).  PRECONDITION: `out` is the solve of exactly these inputs, params, seg_count, set_index, variant and
+    delta.  Nothing can check that: the derivative is stated at out["ctrl"] with the active set of out["lam"], and with
+    another problem's arrays it is the derivative of nothing, returned without an error.  Only the shapes are checked."""
+    if set_index is None and params.dim() != 1:
+        raise ValueError("params must be [20] without set_index, [n_sets, 20] with it")
+    if params.shape[-1] != N_PARAMS:
+        raise ValueError("params rows have %d entries (layout.Shared.as_array() without delta)" % N_PARAMS)
+    if out is not None:
+        B_, S_ = seg.shape[1], seg.shape[2]
+        if out.get("lam") is None or tuple(out["ctrl"].shape) != (B_, 12 * S_) or tuple(out["lam"].shape) != (2, 36, B_, S_) \
+                or tuple(out["status"].shape) != (B_,):
+            raise ValueError("out: the result dict of solve_kept for this batch (ctrl [B, 12 S], lam [2, 36, B, S], status [B])")
+    columns = [int(c) for c in columns]
+    if not columns or min(columns) < 0 or max(columns) >= N_PARAMS:
+        raise ValueError("columns: at least one, each in [0, %d)" % N_PARAMS)
+    d = solver.device
+    seg, init, ref_end, dl_bounds = (_f64(t.detach()).to(d) for t in (seg, init, ref_end, dl_bounds))
+    B = seg.shape[1]
+    if out is None:
+        out = solve_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count=seg_count, set_index=set_index,
+                         variant=variant, delta=delta)
+    rows = params.detach().to(d, torch.float64).reshape(-1, N_PARAMS)
+    sets = [shared_from_params(r, variant, delta) for r in rows.tolist()]
+    T = len(columns)
+    tan = torch.zeros((T, B, N_PARAMS), dtype=torch.float64, device=d)
+    per_cand = rows[set_index.long().clamp(0, rows.shape[0] - 1)] if set_index is not None else rows[:1].expand(B, N_PARAMS)
+    for t, c in enumerate(columns):
+        tan[t, :, c] = per_cand[:, c] if log else 1.0
+    j = solver.solve_jvp(_record(seg, init, ref_end, dl_bounds, seg_count), sets, out, {"shared": tan}, set_index=set_index)
+    return dict(ctrl=out["ctrl"], cost=out["cost"], status=out["status"], dctrl=j["ctrl"], dcost=j["cost"], out=out)
+
+
+def sample_jvp(solver, dctrl, seg, dinit=None, seg_count=None, sel=None, delta=0.1):
+    """Tangents of the sampled trajectories.  Sampling is linear in (ctrl, init), so its Jacobian-vector product is the
+    forward kernel applied to the tangents: dctrl [T, B, 12 S] and dinit [T, B, 6] (None: zero) -> [T, nsel, 6, max_points],
+    one launch over the T B tangent candidates (seg, seg_count and sel as diff.sample, repeated per tangent)."""
+    d = solver.device
+    dctrl, seg = _f64(dctrl.detach()).to(d), _f64(seg.detach()).to(d)
+    T, B = dctrl.shape[0], dctrl.shape[1]
+    di = torch.zeros((T * B, 6), dtype=torch.float64, device=d) if dinit is None else _f64(dinit.detach()).to(d).reshape(T * B, 6)
+    sel = (torch.arange(B, device=d) if sel is None else sel.to(d)).to(torch.int64)
+    sel_rep = (sel[None, :] + B * torch.arange(T, device=d)[:, None]).reshape(-1)
+    cnt = None if seg_count is None else seg_count.repeat(T).contiguous()
+    with torch.no_grad():
+        traj, _ = sample(dctrl.reshape(T * B, -1), seg.repeat(1, T, 1).contiguous(), di, solver, seg_count=cnt, sel=sel_rep, delta=delta)
+    return traj.reshape(T, sel.numel(), 6, traj.shape[2])
+
+
+def eval_states_jvp(solver, dctrl, seg, times, seg_count=None):
+    """Tangents of the evaluated states.  State evaluation is linear in ctrl at fixed times, so its Jacobian-vector product
+    is the forward kernel applied to the tangents: dctrl [T, B, 12 S], times [B, n_times] -> [T, B, 2, n_times, 3]."""
+    d = solver.device
+    dctrl, seg, times = _f64(dctrl.detach()).to(d), _f64(seg.detach()).to(d), _f64(times.detach()).to(d)
+    T, B = dctrl.shape[0], dctrl.shape[1]
+    cnt = None if seg_count is None else seg_count.repeat(T).contiguous()
+    with torch.no_grad():
+        x = eval_states(dctrl.reshape(T * B, -1), seg.repeat(1, T, 1).contiguous(), times.repeat(T, 1).contiguous(), solver, seg_count=cnt)
+    return x.reshape(T, B, 2, times.shape[1], 3)

@@ -60,6 +60,15 @@ class CGrads(C.Structure):
                 ("shared", C.c_void_p)]
 
 
+class CTangents(C.Structure):
+    """btrapz_tangents (include/btrapz_hip.h): device pointers of the input tangents of btrapz_solve_jvp_device."""
+    _fields_ = [("seg", C.c_void_p), ("init", C.c_void_p), ("ref_end", C.c_void_p), ("dl_bounds", C.c_void_p),
+                ("shared", C.c_void_p)]
+
+
+MAX_TANGENTS = 32   # BTRAPZ_MAX_TANGENTS
+
+
 class CWarm(C.Structure):
     """btrapz_warm (include/btrapz_hip.h): optional warm start of a solve."""
     _fields_ = [("x0", C.c_void_p), ("lam0", C.c_void_p), ("lam_out", C.c_void_p),
@@ -127,7 +136,7 @@ EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "bt
            "btrapz_device_count", "btrapz_solve_batch_device", "btrapz_argmin_device",
            "btrapz_sample_device", "btrapz_solve_batch_host", "btrapz_solve_ragged_device",
            "btrapz_corridor_batch_device", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
-           "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_traj_cost_device", "btrapz_traj_cost_vjp_device",
+           "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_solve_jvp_device", "btrapz_traj_cost_device", "btrapz_traj_cost_vjp_device",
            "btrapz_eval_states_device", "btrapz_sample_vjp_device", "btrapz_eval_states_vjp_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
            "btrapz_prism_corridor_batch_device",
            "btrapz_find_traj_last_iterations", "btrapz_argmin_pairs_device", "btrapz_options_init",
@@ -229,6 +238,8 @@ def lib():
                                                C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
         l.btrapz_solve_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, dp,
                                               dp, dp, ip, dp, dp, C.POINTER(CGrads), vp]
+        l.btrapz_solve_jvp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, dp,
+                                              dp, dp, ip, C.c_int, C.POINTER(CTangents), dp, dp, vp]
         l.btrapz_traj_cost_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, ip,
                                               C.c_int, dp, dp, C.c_int, dp, ip, vp]
         l.btrapz_traj_cost_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, ip,
@@ -484,6 +495,21 @@ class Context:
                                                   ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
                                                   ptr(lam), ptr(status), ptr(ctrl_bar), ptr(cost_bar), C.byref(grads),
                                                   C.c_void_p(stream or 0)), "btrapz_solve_vjp_device")
+
+    def solve_jvp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                         T, seg_dot=None, init_dot=None, ref_end_dot=None, dl_bounds_dot=None, shared_dot=None,
+                         ctrl_dot=None, cost_dot=None, stream=None):
+        """btrapz_solve_jvp_device: directional derivatives of a solve (elastic = 0, multipliers kept) along T tangents per
+        candidate.  sets / set_index / seg_count as in solve_vjp_device; the *_dot device tensors carry a leading axis T
+        (None: zero); ctrl_dot [T, B, 12 seg_stride] / cost_dot [T, B] are overwritten (either may be None)."""
+        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
+        raw = lambda t: t.data_ptr() if t is not None else None
+        tan = CTangents(raw(seg_dot), raw(init_dot), raw(ref_end_dot), raw(dl_bounds_dot), raw(shared_dot))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_solve_jvp_device(self._h, arr, len(sets), ptr(set_index), B, seg_stride, ptr(seg),
+                                                  ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
+                                                  ptr(lam), ptr(status), int(T), C.byref(tan), ptr(ctrl_dot), ptr(cost_dot),
+                                                  C.c_void_p(stream or 0)), "btrapz_solve_jvp_device")
 
     def traj_cost_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
                          ref_stride, a_cost, n_points=None, stream=None):

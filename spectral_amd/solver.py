@@ -257,6 +257,44 @@ class BatchSolver:
                                   g_ref_end=g["ref_end"], g_dl_bounds=g["dl_bounds"], g_shared=g["shared"], stream=stream)
         return g
 
+    def solve_jvp(self, dbatch_or_rec, shared_or_sets, out, tangents, set_index=None):
+        """Directional derivatives of a solve (btrapz_solve_jvp_device): T input directions per candidate, one launch, one
+        factorisation per axis problem.  dbatch_or_rec, shared_or_sets, out, set_index: as in solve_vjp.  tangents: a dict
+        with any of "seg" [T, NUM_SEG_FIELDS, B, S] (field 0 is ignored), "init" [T, B, 6], "ref_end" [T, B, 2],
+        "dl_bounds" [T, B, 10], "shared" [T, B, 20] (per candidate, layout.Shared.as_array order without delta); a missing
+        one is zero.  Returns {"ctrl": [T, B, 12 S], "cost": [T, B]}, device tensors."""
+        if isinstance(dbatch_or_rec, dict):
+            B, S, seg_count = dbatch_or_rec["B"], dbatch_or_rec["seg_stride"], dbatch_or_rec["seg_count"]
+            seg, init, ref_end, dl = (dbatch_or_rec[k] for k in ("seg", "init", "ref_end", "dl_bounds"))
+        else:
+            B, S, seg_count = dbatch_or_rec.B, dbatch_or_rec.S, None
+            seg, init, ref_end, dl = dbatch_or_rec.seg, dbatch_or_rec.init, dbatch_or_rec.ref_end, dbatch_or_rec.dl_bounds
+        sets = list(shared_or_sets) if isinstance(shared_or_sets, (list, tuple)) else [shared_or_sets]
+        if set_index is not None:
+            assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
+        if out.get("lam") is None:
+            raise ValueError("solve_jvp needs the solve's multipliers: solve with keep_multipliers=True")
+        unknown = set(tangents) - {"seg", "init", "ref_end", "dl_bounds", "shared"}
+        if unknown:
+            raise ValueError("unknown tangents: %s" % sorted(unknown))
+        given = {k: v for k, v in tangents.items() if v is not None}
+        T = next(iter(given.values())).shape[0] if given else 0
+        d = self.device
+        shapes = dict(seg=(T, L.NUM_SEG_FIELDS, B, S), init=(T, B, 6), ref_end=(T, B, 2), dl_bounds=(T, B, 10), shared=(T, B, 20))
+        tan = {}
+        for k, v in given.items():
+            if tuple(v.shape) != shapes[k]:
+                raise ValueError("tangent %r: shape %s, expected %s" % (k, tuple(v.shape), shapes[k]))
+            tan[k] = v.to(d, dtype=torch.float64).contiguous()
+        o = dict(ctrl=torch.empty((max(T, 0), B, 12 * S), dtype=torch.float64, device=d),
+                 cost=torch.empty((max(T, 0), B), dtype=torch.float64, device=d))
+        stream = torch.cuda.current_stream(d).cuda_stream
+        self.ctx.solve_jvp_device(B, S, sets, set_index, seg, seg_count, init, ref_end, dl, out["ctrl"], out["lam"],
+                                  out["status"], T, seg_dot=tan.get("seg"), init_dot=tan.get("init"),
+                                  ref_end_dot=tan.get("ref_end"), dl_bounds_dot=tan.get("dl_bounds"),
+                                  shared_dot=tan.get("shared"), ctrl_dot=o["ctrl"], cost_dot=o["cost"], stream=stream)
+        return o
+
     def _cost_args(self, rec, shared_or_sets, ctrl, s_ref, l_ref, status, set_index):
         if isinstance(rec, dict):
             B, S, seg_count, seg, init = rec["B"], rec["seg_stride"], rec["seg_count"], rec["seg"], rec["init"]

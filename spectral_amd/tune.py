@@ -147,3 +147,91 @@ def fit_trajectory(solver, kb, variant, target, weights, starts=16, steps=100, s
     return dict(start_mean=means[0], final_mean=means[-1], best=best, means=means, solves=starts * (steps + 1),
                 losses=final.cpu().numpy(), max_dev=dev[b].abs().amax(dim=1).cpu().numpy(), samples=state["n"],
                 weights=w_rows[:, list(ROW_OF_WEIGHT)])
+
+
+def fit_trajectory_lm(solver, kb, variant, target, weights, starts=16, steps=25, seed=0, spread=float(np.log(1.3)),
+                      columns=(0, 1, 2, 3, 4, 5), damping=1e-2, damping_range=(1e-7, 1e7)):
+    """fit_trajectory's problem -- the same starts (weights, seed, spread), the same loss -- by Levenberg-Marquardt on the
+    ten log-weights: it is a least-squares problem with ten unknowns, and forward mode gives its Jacobian from ONE
+    factorisation per axis problem.  Every start is a parameter set of one batched launch.  Per step: the Jacobian of the
+    control points with respect to the ten log-weights at the current weights (diff.solve_jacobian, log=True, on the solve
+    the previous step accepted), through the sampling (diff.sample_jvp) to the residuals' J [m, 10] per start; the damped
+    normal equations (J'J + damping mean(diag J'J) I) step = -J'r per start (torch, 10 x 10); a trial solve of every
+    start at its stepped weights, projected on BOX; per start, accept when the loss fell (damping / 3) or keep the old
+    point (damping x 4).  The weights are determined only up to one factor per axis (fit_trajectory), so J'J has a
+    two-dimensional null space: the damping is kept inside damping_range and never reaches 0.
+
+    Returns fit_trajectory's dict.  "solves" counts every candidate solved, trial solves included: starts (steps + 1);
+    "jvp_launches" is the number of JVP launches (steps), each over the `starts` candidates; "accepted" the accepted
+    steps per start."""
+    d = solver.device
+    W = np.clip(np.asarray(weights, dtype=np.float64)[:10], *BOX)
+    rec = replicated_record(solver, kb, variant, starts)
+    rng = np.random.default_rng(seed)
+    w0 = W[None, :] * np.exp(spread * rng.choice([-1.0, 1.0], (starts, 10)))
+    rows = np.stack([diff.params_from_shared(shared_of(w, kb.header, kb.delta, variant)) for w in np.clip(w0, *BOX)])
+    U = torch.tensor(np.log(rows[:, :10]), dtype=torch.float64, device=d)
+    rest = torch.tensor(rows[:, 10:], dtype=torch.float64, device=d)
+    idx = torch.arange(starts, dtype=torch.int32, device=d)
+    tgt = torch.as_tensor(np.asarray(target, dtype=np.float64), device=d)
+    cols = torch.tensor(sorted(int(c) for c in columns), dtype=torch.long, device=d)
+    lo, hi = float(np.log(BOX[0])), float(np.log(BOX[1]))
+    args = (rec["seg"], rec["init"], rec["ref_end"], rec["dl_bounds"])
+    kw = dict(seg_count=rec["seg_count"], set_index=idx, variant=variant, delta=kb.delta)
+    state = {}
+
+    def solve_at(Uc):
+        o = diff.solve_kept(solver, *args, torch.cat([torch.exp(Uc), rest], dim=1), **kw)
+        traj, npts = diff.sample(o["ctrl"], rec["seg"], rec["init"], solver, seg_count=rec["seg_count"], delta=kb.delta)
+        if "n" not in state:
+            state["n"] = min(int(tgt.shape[1]), int(traj.shape[2]), int(npts.min().item()))
+        dev = traj[:, :, :state["n"]] - tgt[None, :, :state["n"]]
+        ok = (o["status"] == 1) | (o["status"] == 2)
+        loss = torch.where(ok, (dev[:, cols] ** 2).mean(dim=(1, 2)), torch.full((starts,), float("inf"), dtype=torch.float64, device=d))
+        return o, dev, loss
+
+    def mean_of(loss):
+        l = loss[torch.isfinite(loss)]
+        return float(l.mean()) if l.numel() else float("nan")
+
+    out, dev, loss = solve_at(U)
+    lam = torch.full((starts,), float(damping), dtype=torch.float64, device=d)
+    accepted = torch.zeros(starts, dtype=torch.int64, device=d)
+    means = [mean_of(loss)]
+    eye = torch.eye(10, dtype=torch.float64, device=d)
+    for _ in range(steps):
+        jac = diff.solve_jacobian(solver, *args, torch.cat([torch.exp(U), rest], dim=1), range(10), log=True, out=out, **kw)
+        dtraj = diff.sample_jvp(solver, jac["dctrl"], rec["seg"], seg_count=rec["seg_count"], delta=kb.delta)
+        n = state["n"]
+        J = dtraj[:, :, cols, :n].permute(1, 2, 3, 0).reshape(starts, -1, 10)      # [starts, m, 10]
+        r = dev[:, cols].reshape(starts, -1)                                       # [starts, m]
+        live = torch.isfinite(loss)
+        J = torch.where(live[:, None, None], J, torch.zeros_like(J))
+        r = torch.where(live[:, None], r, torch.zeros_like(r))
+        A = J.transpose(1, 2) @ J
+        g = (J.transpose(1, 2) @ r[:, :, None])[:, :, 0]
+        scale = A.diagonal(dim1=1, dim2=2).mean(dim=1)
+        usable = live & (scale > 0) & torch.isfinite(scale)
+        # (a start without a solve, or whose Jacobian vanishes, gets the identity system: step 0, never a singular member)
+        Ad = torch.where(usable[:, None, None], A + (lam * scale)[:, None, None] * eye, eye.expand(starts, 10, 10))
+        g = torch.where(usable[:, None], g, torch.zeros_like(g))
+        step = -torch.linalg.solve(Ad, g[:, :, None])[:, :, 0]
+        U_try = (U + step).clamp(lo, hi)
+        o_t, dev_t, loss_t = solve_at(U_try)
+        acc = live & torch.isfinite(loss_t) & (loss_t < loss)
+        U = torch.where(acc[:, None], U_try, U)
+        dev = torch.where(acc[:, None, None], dev_t, dev)
+        loss = torch.where(acc, loss_t, loss)
+        out = dict(out)
+        out["ctrl"] = torch.where(acc[:, None], o_t["ctrl"], out["ctrl"])
+        out["lam"] = torch.where(acc[None, None, :, None], o_t["lam"], out["lam"])
+        out["status"] = torch.where(acc, o_t["status"], out["status"])
+        out["cost"] = torch.where(acc, o_t["cost"], out["cost"])
+        lam = torch.where(acc, lam / 3.0, lam * 4.0).clamp(*damping_range)
+        accepted += acc.long()
+        means.append(mean_of(loss))
+    b = int(torch.argmin(loss).item())   # (every start failed: start 0, loss inf)
+    w_rows = torch.exp(U).cpu().numpy()
+    return dict(start_mean=means[0], final_mean=means[-1], best=float(loss.min()), means=means, solves=starts * (steps + 1),
+                jvp_launches=steps, accepted=accepted.cpu().numpy(), losses=loss.cpu().numpy(),
+                max_dev=dev[b].abs().amax(dim=1).cpu().numpy(), samples=state["n"], weights=w_rows[:, list(ROW_OF_WEIGHT)])

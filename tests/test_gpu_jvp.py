@@ -1,0 +1,537 @@
+"""btrapz_solve_jvp_device (directional derivatives of a batched solve) on the GPU: against the oracle yardstick
+(tests/jvp_reference.py), against the existing VJP by the adjoint identity, defined cases, structure (T tangents = T
+calls, uniform = ragged, sets = single sets, all bit for bit), central differences of the GPU solve, the Python layers
+(diff.solve_jacobian, diff.sample_jvp, diff.eval_states_jvp), refusals, and the Levenberg-Marquardt fit against the Adam
+fit of the same run."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from jvp_reference import KEYS, Tangent
+from spectral_amd import diff, layout as L, synth, tune
+from spectral_amd.native import MAX_TANGENTS, BtrapzError
+from vjp_reference import Adjoint, one
+
+pytestmark = pytest.mark.gpu
+
+B = 256
+FAMILIES = {
+    "generic": lambda S, seed: synth.make_batch(B, S, config=3, variant=0, seed=seed),
+    "scenario_1": lambda S, seed: synth.make_scenario1_batch(B, S, 0, seed=seed),
+    "cuboid": lambda S, seed: synth.make_scenario1_batch(B, S, 1, seed=seed),
+}
+SHAPES = lambda T, B_, S: dict(seg=(T, L.NUM_SEG_FIELDS, B_, S), init=(T, B_, 6), ref_end=(T, B_, 2), dl_bounds=(T, B_, 10),
+                               shared=(T, B_, 20))
+
+
+@pytest.fixture(scope="module")
+def solver():
+    from spectral_amd.solver import BatchSolver
+    return BatchSolver(0)
+
+
+def _solve(solver, batch, sh, lean=0):
+    db = solver.upload(batch)
+    d = solver.device
+    o = solver.solve(db, sh, keep_multipliers=True, lean=lean, out={
+        "ctrl": torch.zeros((batch.B, 12 * batch.S), dtype=torch.float64, device=d),
+        "cost": torch.empty(batch.B, dtype=torch.float64, device=d),
+        "status": torch.empty(batch.B, dtype=torch.int32, device=d),
+        "iters": torch.empty(batch.B, dtype=torch.int32, device=d)})
+    return db, o
+
+
+def _directions(rng, T, B_, S, keys=KEYS):
+    """Dense random tangents [T, ...] in the named arrays (numpy); field 0 of seg random too: it must be ignored."""
+    return {k: rng.standard_normal(SHAPES(T, B_, S)[k]) for k in keys}
+
+
+def _dev(solver, tan):
+    return {k: torch.tensor(v, device=solver.device) for k, v in tan.items()}
+
+
+def _ragged(solver, batch, W, counts):
+    """The batch in a ragged record of stride W with the given segment counts (candidates keep their first count segments)."""
+    d = solver.device
+    seg = np.zeros((L.NUM_SEG_FIELDS, batch.B, W)); seg[:, :, :batch.S] = batch.seg
+    return dict(B=batch.B, seg_stride=W, seg=torch.tensor(seg, device=d), seg_count=torch.tensor(counts, dtype=torch.int32, device=d),
+                init=torch.tensor(batch.init, device=d), ref_end=torch.tensor(batch.ref_end, device=d),
+                dl_bounds=torch.tensor(batch.dl_bounds, device=d))
+
+
+FLOOR = 1e-3
+
+
+def _per_tangent_ratios(cd, cs, ref_x, ref_c):
+    """Errors of ctrl_dot [T, 12 S] and cost_dot [T] of one candidate, each tangent relative to ITS OWN reference's largest
+    entry.  A tangent whose reference is (nearly) 0 is measured against FLOOR = 1e-3 of the candidate's largest tangent.
+    The floor comes from the yardstick's own error: its least-squares solve of the singular KKT matrix differs from a
+    null-space solve of the same system by up to 7e-8 of the largest tangent (64 segments, CPU only), so a reference
+    of exactly 0 comes back as 1e-10 to 1e-8, and 1e-4 x 1e-3 = 1e-7 of the largest tangent is what it can certify."""
+    nx = np.abs(ref_x).max(1); nc = np.abs(ref_c)
+    sx = np.maximum(nx, max(FLOOR * nx.max(), 1e-300)); sc = np.maximum(nc, max(FLOOR * nc.max(), 1e-300))
+    return np.abs(cd - ref_x).max(1) / sx, np.abs(cs - ref_c) / sc
+
+
+def _fmt(v):
+    return "[" + " ".join("%.1e" % x for x in np.atleast_1d(v)) + "]"
+
+
+@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("S", [1, 2, 10, 20, 64])
+def test_jvp_against_the_yardstick(solver, family, S):
+    """Families, seeds, S and the candidates per S (n_cmp) of test_gpu_vjp.py::test_vjp_against_the_yardstick; tangent 0 is
+    dense in all five arrays at once, tangents 1-5 in one array each.  ctrl_dot and cost_dot within 1e-4 of the array's
+    norm per candidate AND tangent (_per_tangent_ratios) on strictly complementary candidates.
+
+    Measured on an MI355X: worst ratio over all cases and tangents 7.9e-6.  (Mostly the yardstick's own rounding in dP x:
+    tests/jvp_reference.py.)"""
+    batch, sh = FAMILIES[family](S, 100 + S)
+    rng = np.random.default_rng(S)
+    T = 6
+    tan = {k: np.zeros(SHAPES(T, B, S)[k]) for k in KEYS}
+    for k in KEYS:
+        tan[k][0] = rng.standard_normal(tan[k][0].shape)
+    for t, k in enumerate(KEYS):
+        tan[k][1 + t] = rng.standard_normal(tan[k][0].shape)
+    n_cmp = {1: 4, 2: 4, 10: 3, 20: 2, 64: 1}[S]
+    st0 = None
+    picked = []
+    seen = np.zeros(T)
+    for lean in (-1, 1):
+        db, o = _solve(solver, batch, sh, lean=lean)
+        st = o["status"].cpu().numpy()
+        if st0 is None:
+            st0 = st
+            # the candidates compared, and their directions with the entries of non-unique derivatives (two fields tie at
+            # a joint; the cuboid's kink) set to 0
+            for b in np.flatnonzero(st == 1)[:8 * n_cmp]:
+                bt = one(batch, b)
+                adj = Adjoint(bt, sh, np.zeros(12 * S), 0.0)
+                if not adj.strict:
+                    continue
+                adj.grads()
+                um = adj.unique_mask()
+                tan["seg"][:, :, b, :] *= um["seg"][None]
+                for k in ("init", "ref_end", "dl_bounds", "shared"):
+                    tan[k][:, b] *= um[k][None]
+                picked.append((b, bt, adj))
+                if len(picked) >= n_cmp:
+                    break
+            assert len(picked) >= n_cmp, (family, S, len(picked))
+        j = solver.solve_jvp(db, sh, o, _dev(solver, tan))
+        torch.cuda.synchronize()
+        cd, cs = j["ctrl"].cpu().numpy(), j["cost"].cpu().numpy()
+        bad = (st != 1) & (st != 2)
+        assert (cd[:, bad] == 0).all() and (cs[:, bad] == 0).all()
+        worst = 0.0
+        for b, bt, adj in picked:
+            ref_x = np.zeros((T, 12 * S)); ref_c = np.zeros(T)
+            for t in range(T):
+                dr = {k: (tan[k][t, :, b, :] if k == "seg" else tan[k][t, b]).copy() for k in KEYS}
+                dr["seg"][L.F_T] = 0.0
+                tg = Tangent(bt, sh, dr, adj=adj)
+                ref_x[t], ref_c[t] = tg.dx, tg.dcost
+            ex, ec = _per_tangent_ratios(cd[:, b], cs[:, b], ref_x, ref_c)
+            worst = max(worst, ex.max(), ec.max())
+            print("yardstick %s S=%d lean=%d b=%d: ctrl_dot %s cost_dot %s of each tangent's norm; |ref dx| %s" %
+                  (family, S, lean, b, _fmt(ex), _fmt(ec), _fmt(np.abs(ref_x).max(1))))
+            assert (ex <= 1e-4).all() and (ec <= 1e-4).all(), (family, S, lean, b, ex, ec)
+            seen = np.maximum(seen, np.abs(ref_x).max(1))
+        print("yardstick %s S=%d lean=%d: worst ratio %.3e" % (family, S, lean, worst))
+    # 0 == 0 is no agreement: the dense tangent and the seg, init and shared tangents must have moved a compared candidate
+    # (ref_end moves nothing where d_ref is 0; no l-axis velocity row is active in these families: dl_bounds has a test of
+    # its own, test_dl_bounds_tangent_on_active_rows)
+    assert (seen[[0, 1, 2, 5]] > 0).all(), seen
+
+
+def _identity(solver, rec, sets, o, set_index, S, T=3, seed=0, keys=KEYS):
+    rng = np.random.default_rng(seed)
+    Bn = rec["B"] if isinstance(rec, dict) else rec.B
+    d = solver.device
+    tan = _directions(rng, T, Bn, S)
+    for k in KEYS:
+        if k not in keys:
+            tan[k][:] = 0.0
+    xbar = rng.standard_normal((Bn, 12 * S)); cbar = rng.standard_normal(Bn)
+    g = solver.solve_vjp(rec, sets, o, torch.tensor(xbar, device=d), torch.tensor(cbar, device=d), set_index=set_index)
+    j = solver.solve_jvp(rec, sets, o, _dev(solver, tan), set_index=set_index)
+    torch.cuda.synchronize()
+    g = {k: v.cpu().numpy() for k, v in g.items()}
+    cd, cs = j["ctrl"].cpu().numpy(), j["cost"].cpu().numpy()
+    st = o["status"].cpu().numpy()
+    solved = (st == 1) | (st == 2)
+    assert solved.sum() >= Bn // 2
+    worst = 0.0
+    for t in range(T):
+        lhs = (xbar * cd[t]).sum(1) + cbar * cs[t]
+        mag = (np.abs(xbar) * np.abs(cd[t])).sum(1) + np.abs(cbar) * np.abs(cs[t])
+        rhs = (np.moveaxis(g["seg"], 1, 0) * np.moveaxis(tan["seg"][t], 1, 0)).sum((1, 2))
+        for k in ("init", "ref_end", "dl_bounds", "shared"):
+            rhs = rhs + (g[k] * tan[k][t]).sum(1)
+        ratio = np.abs(lhs - rhs)[solved] / np.maximum(mag[solved], 1e-300)
+        worst = max(worst, float(ratio.max()))
+    return worst
+
+
+def test_adjoint_identity_against_the_vjp(solver):
+    """<ctrl_bar, ctrl_dot> + <cost_bar, cost_dot> = <grad, direction> per candidate, on EVERY solved candidate, within 1e-4
+    of sum |ctrl_bar| |ctrl_dot| + |cost_bar| |cost_dot|: uniform, ragged and three-set batches, both variants."""
+    d = solver.device
+    worst = {}
+    for variant in (0, 1):
+        S = 20
+        batch, sh = synth.make_scenario1_batch(B, S, variant, seed=70 + variant)
+        db, o = _solve(solver, batch, sh)
+        worst["uniform", variant] = _identity(solver, db, sh, o, None, S, seed=1)
+        # ragged: stride 16, the first 5..10 segments of every candidate
+        b10, sh10 = synth.make_scenario1_batch(B, 10, variant, seed=72 + variant)
+        rec = _ragged(solver, b10, 16, 5 + np.arange(B) % 6)
+        idx0 = torch.zeros(B, dtype=torch.int32, device=d)
+        orag = solver.solve_sets_ragged(rec, [sh10], idx0, keep_multipliers=True)
+        worst["ragged", variant] = _identity(solver, rec, [sh10], orag, idx0, 16, seed=2)
+        # three sets
+        base = sh.as_array()
+        sets = []
+        for jn in range(3):
+            row = base[:20].copy(); row[:8] *= 1.0 + 0.2 * jn
+            sets.append(diff.shared_from_params(row, variant, sh.delta))
+        set_index = torch.tensor(np.arange(B, dtype=np.int32) % 3, device=d)
+        os_ = {k: v.clone() for k, v in solver.solve_sets(db, sets, set_index, keep_multipliers=True).items()}
+        worst["sets", variant] = _identity(solver, db, sets, os_, set_index, S, seed=3)
+    for k, v in worst.items():
+        print("adjoint identity %s variant %d: worst |lhs - rhs| / sum |terms| = %.3e" % (k + (v,)))
+    assert max(worst.values()) <= 1e-4, worst
+
+
+def test_defined_cases(solver):
+    S = 10
+    d = solver.device
+    batch, sh = synth.make_scenario1_batch(B, S, 0, seed=81)
+    batch.dl_bounds[:, 2] = -1e10; batch.dl_bounds[:, 3] = 1e10   # far bounds (the reference's default rows)
+    db, o = _solve(solver, batch, sh)
+    rng = np.random.default_rng(8)
+    tan = _directions(rng, 2, B, S)
+    st = o["status"].clone(); st[3] = 0; st[4] = 5; st[9] = -1
+    o2 = dict(o); o2["status"] = st
+    j = solver.solve_jvp(db, sh, o2, _dev(solver, tan))
+    for b in (3, 4, 9):
+        assert (j["ctrl"][:, b] == 0).all() and (j["cost"][:, b] == 0).all()
+    solved = (st == 1) | (st == 2)
+    assert solved.any() and (j["ctrl"][:, solved] != 0).any()
+    # a tangent in field 0 changes nothing, bit for bit; neither does a tangent on a far bound
+    t2 = {k: v.copy() for k, v in tan.items()}
+    t2["seg"][:, L.F_T] = 0.0
+    t2["dl_bounds"][:, :, 2:4] = 0.0
+    j2 = solver.solve_jvp(db, sh, o2, _dev(solver, t2))
+    assert torch.equal(j["ctrl"], j2["ctrl"]) and torch.equal(j["cost"], j2["cost"])
+    # a bad set index and a bad segment count: exact zeros; slots beyond 12 S_b: 0
+    counts = 5 + np.arange(B) % 6
+    counts[7] = 0; counts[8] = 17
+    rec = _ragged(solver, batch, 16, counts)
+    idx = np.zeros(B, dtype=np.int32); idx[11] = 3; idx[12] = -1
+    set_index = torch.tensor(idx, device=d)
+    orag = solver.solve_sets_ragged(rec, [sh], set_index, keep_multipliers=True)
+    forced = dict(orag); forced["status"] = orag["status"].clone()
+    forced["status"][[7, 8, 11, 12]] = 1   # (even if the status claimed a solve)
+    tr = _directions(rng, 2, B, 16)
+    jr = solver.solve_jvp(rec, [sh], forced, _dev(solver, tr), set_index=set_index)
+    for b in (7, 8, 11, 12):
+        assert (jr["ctrl"][:, b] == 0).all() and (jr["cost"][:, b] == 0).all(), b
+    cd = jr["ctrl"].cpu().numpy()
+    for b in range(B):
+        if 1 <= counts[b] <= 16:
+            assert (cd[:, b, 12 * counts[b]:] == 0).all(), b
+    assert torch.isfinite(jr["ctrl"]).all() and torch.isfinite(jr["cost"]).all()
+
+
+def test_structure(solver):
+    S, W, T = 10, 16, 5
+    d = solver.device
+    batch, sh = synth.make_scenario1_batch(B, S, 0, seed=7)
+    db, o = _solve(solver, batch, sh, lean=-1)
+    before = {k: o[k].clone() for k in ("ctrl", "cost", "status", "lam")}
+    rng = np.random.default_rng(1)
+    xbar = torch.tensor(rng.standard_normal((B, 12 * S)), device=d); cbar = torch.tensor(rng.standard_normal(B), device=d)
+    g0 = {k: v.clone() for k, v in solver.solve_vjp(db, sh, o, xbar, cbar).items()}
+    tan = _directions(rng, T, B, S)
+    j = solver.solve_jvp(db, sh, o, _dev(solver, tan))
+    # two identical calls; the solve's outputs and the VJP's gradients untouched by a JVP in between
+    j_again = solver.solve_jvp(db, sh, o, _dev(solver, tan))
+    assert torch.equal(j["ctrl"], j_again["ctrl"]) and torch.equal(j["cost"], j_again["cost"])
+    for k, v in before.items():
+        assert torch.equal(o[k], v), k
+    g1 = solver.solve_vjp(db, sh, o, xbar, cbar)
+    for k in g0:
+        assert torch.equal(g0[k], g1[k]), k
+    # T tangents in one call = T calls of one tangent
+    for t in range(T):
+        jt = solver.solve_jvp(db, sh, o, _dev(solver, {k: v[t:t + 1] for k, v in tan.items()}))
+        assert torch.equal(jt["ctrl"][0], j["ctrl"][t]) and torch.equal(jt["cost"][0], j["cost"][t]), t
+    # uniform = ragged (the same solve laid out for the wider stride)
+    rec = _ragged(solver, batch, W, np.full(B, S))
+    cr = torch.zeros((B, 12 * W), dtype=torch.float64, device=d); cr[:, :12 * S] = o["ctrl"]
+    lam = torch.zeros((2, 36, B, W), dtype=torch.float64, device=d); lam[..., :S] = o["lam"]
+    tr = {k: v.copy() for k, v in tan.items()}
+    tr["seg"] = np.zeros((T, L.NUM_SEG_FIELDS, B, W)); tr["seg"][..., :S] = tan["seg"]
+    jr = solver.solve_jvp(rec, sh, dict(ctrl=cr, lam=lam, status=o["status"]), _dev(solver, tr))
+    assert torch.equal(jr["ctrl"][:, :, :12 * S], j["ctrl"]) and (jr["ctrl"][:, :, 12 * S:] == 0).all()
+    assert torch.equal(jr["cost"], j["cost"])
+    # three sets = three single-set calls
+    base = sh.as_array()
+    sets = []
+    for jn in range(3):
+        row = base[:20].copy(); row[:8] *= 1.0 + 0.2 * jn
+        sets.append(diff.shared_from_params(row, 0, sh.delta))
+    idx = np.arange(B, dtype=np.int32) % 3
+    set_index = torch.tensor(idx, device=d)
+    os_ = {k: v.clone() for k, v in solver.solve_sets(db, sets, set_index, keep_multipliers=True, lean=-1).items()}
+    js = solver.solve_jvp(db, sets, os_, _dev(solver, tan), set_index=set_index)
+    for jn in range(3):
+        j1 = solver.solve_jvp(db, [sets[jn]], os_, _dev(solver, tan), set_index=torch.zeros(B, dtype=torch.int32, device=d))
+        sel = torch.tensor(idx == jn, device=d)
+        assert torch.equal(js["ctrl"][:, sel], j1["ctrl"][:, sel]) and torch.equal(js["cost"][:, sel], j1["cost"][:, sel]), jn
+
+
+def test_gpu_central_differences(solver):
+    """Central differences of the GPU solve along a direction, on test_gpu_vjp.py::test_gpu_finite_differences' batch and
+    at its 1e-3: ctrl_dot relative to the derivative's largest entry per candidate, cost_dot relative to the sum of the
+    magnitudes of the terms it is summed from (strictly complementary candidates)."""
+    S = 20
+    batch, sh = synth.make_scenario1_batch(64, S, 0, seed=41)
+    d = solver.device
+    db, o = _solve(solver, batch, sh)
+    st = o["status"].cpu().numpy()
+    rng = np.random.default_rng(4)
+    tan = _directions(rng, 1, 64, S)
+    tan["seg"][:, L.F_T] = 0.0
+    picked = []
+    for b in np.flatnonzero(st == 1):
+        adj = Adjoint(one(batch, b), sh, np.zeros(12 * S), 0.0)
+        if not adj.strict:
+            continue
+        adj.grads()
+        um = adj.unique_mask()
+        tan["seg"][0, :, b, :] *= um["seg"]
+        for k in ("init", "ref_end", "dl_bounds", "shared"):
+            tan[k][0, b] *= um[k]
+        picked.append(b)
+        if len(picked) >= 8:
+            break
+    assert len(picked) >= 4
+    j = solver.solve_jvp(db, sh, o, _dev(solver, tan))
+    cd, cs = j["ctrl"].cpu().numpy()[0], j["cost"].cpu().numpy()[0]
+    h = 1e-5
+    arr = diff.params_from_shared(sh)
+    fdx = np.zeros((64, 12 * S)); fdc = np.zeros(64)
+    for b in picked:   # (the shared tangent is per candidate: one pair of solves per candidate)
+        res = []
+        for sgn in (1.0, -1.0):
+            bt = L.Batch(B=64, S=S, seg=batch.seg + sgn * h * tan["seg"][0], init=batch.init + sgn * h * tan["init"][0],
+                         ref_end=batch.ref_end + sgn * h * tan["ref_end"][0], dl_bounds=batch.dl_bounds + sgn * h * tan["dl_bounds"][0])
+            oo = solver.solve(solver.upload(bt), diff.shared_from_params(arr + sgn * h * tan["shared"][0, b], 0, sh.delta))
+            torch.cuda.synchronize()
+            res.append((oo["ctrl"][b].cpu().numpy(), float(oo["cost"][b])))
+        fdx[b] = (res[0][0] - res[1][0]) / (2 * h); fdc[b] = (res[0][1] - res[1][1]) / (2 * h)
+    for b in picked:
+        scale = max(np.abs(cd[b]).max(), np.abs(fdx[b]).max())
+        ex = np.abs(cd[b] - fdx[b]).max() / scale
+        # cost_dot is a sum of terms that cancel: relative to the sum of their magnitudes (Tangent.dcost_scale, as on the CPU)
+        dr = {k: (tan[k][0, :, b, :] if k == "seg" else tan[k][0, b]).copy() for k in KEYS}
+        cscale = Tangent(one(batch, b), sh, dr).dcost_scale
+        ec = abs(cs[b] - fdc[b]) / cscale
+        print("central differences b=%d: ctrl_dot %.3e of the largest entry; cost_dot %.6e against %.6e: %.3e of the terms' %.3e" %
+              (b, ex, cs[b], fdc[b], ec, cscale))
+        assert ex <= 1e-3, (b, ex)
+        assert ec <= 1e-3, (b, cs[b], fdc[b], cscale)
+
+
+def test_python_layers(solver):
+    S = 10
+    batch, sh = synth.make_scenario1_batch(64, S, 0, seed=31)
+    d = solver.device
+    tt = lambda a: torch.tensor(a, device=d)
+    seg, init, ref_end, dl = tt(batch.seg), tt(batch.init), tt(batch.ref_end), tt(batch.dl_bounds)
+    params = tt(diff.params_from_shared(sh))
+    cols = [0, 3, 5, 9, 10]
+    jac = diff.solve_jacobian(solver, seg, init, ref_end, dl, params, cols, variant=0, delta=sh.delta)
+    db = solver.upload(batch)
+    unit = torch.zeros((len(cols), 64, 20), dtype=torch.float64, device=d)
+    for t, c in enumerate(cols):
+        unit[t, :, c] = 1.0
+    j = solver.solve_jvp(db, sh, jac["out"], {"shared": unit})
+    assert torch.equal(jac["dctrl"], j["ctrl"]) and torch.equal(jac["dcost"], j["cost"])
+    jl = diff.solve_jacobian(solver, seg, init, ref_end, dl, params, cols, variant=0, delta=sh.delta, log=True, out=jac["out"])
+    j2 = solver.solve_jvp(db, sh, jac["out"], {"shared": unit * params[None, None, :]})
+    assert torch.equal(jl["dctrl"], j2["ctrl"]) and torch.equal(jl["dcost"], j2["cost"])
+    # sample_jvp / eval_states_jvp against the difference quotient of two solves along a weight direction
+    w = torch.zeros(20, dtype=torch.float64, device=d); w[:10] = tt(np.random.default_rng(2).standard_normal(10)) * params[:10] * 0.1
+    jw = solver.solve_jvp(db, sh, jac["out"], {"shared": w[None, None, :].expand(1, 64, 20).contiguous()})
+    dtraj = diff.sample_jvp(solver, jw["ctrl"], seg, delta=sh.delta)[0]
+    times = torch.linspace(0.0, 1.5, 7, dtype=torch.float64, device=d)[None, :].expand(64, 7).contiguous()
+    dx = diff.eval_states_jvp(solver, jw["ctrl"], seg, times)[0]
+    h = 1e-5
+    with torch.no_grad():
+        outs = []
+        for sgn in (1.0, -1.0):
+            c, _, s_ = diff.solve(solver, seg, init, ref_end, dl, params + sgn * h * w, variant=0, delta=sh.delta)
+            outs.append((diff.sample(c, seg, init, solver, delta=sh.delta)[0], diff.eval_states(c, seg, times, solver), s_))
+    ok = ((jac["status"] == 1) & (outs[0][2] == 1) & (outs[1][2] == 1)).cpu().numpy()
+    # (strictly complementary candidates, as the central differences of the solve: elsewhere only one-sided derivatives)
+    strict = [b for b in np.flatnonzero(ok) if Adjoint(one(batch, b), sh, np.zeros(12 * S), 0.0).strict][:8]
+    assert len(strict) >= 4
+    ok = np.zeros(64, bool); ok[strict] = True
+    for mine, fd, what in ((dtraj, (outs[0][0] - outs[1][0]) / (2 * h), "sample_jvp"), (dx, (outs[0][1] - outs[1][1]) / (2 * h), "eval_states_jvp")):
+        m, f = mine.cpu().numpy().reshape(64, -1)[ok], fd.cpu().numpy().reshape(64, -1)[ok]
+        scale = np.maximum(np.abs(m).max(1), np.abs(f).max(1))
+        ratio = np.abs(m - f).max(1) / np.maximum(scale, 1e-3 * scale.max())
+        print("%s against the difference quotient: worst %.3e over %d candidates" % (what, ratio.max(), ok.sum()))
+        assert (ratio <= 1e-3).all(), (what, ratio)
+
+
+REFUSALS = ("seg_stride", "ctrl", "lam", "status", "outputs", "tangents", "T_zero", "T_above_cap", "variant", "delta")
+
+
+@pytest.mark.parametrize("case", REFUSALS)
+def test_refusals(solver, case):
+    """One refusal per case: BtrapzError with BTRAPZ_EINVAL (-1) and the text that names the reason."""
+    import dataclasses
+    d = solver.device
+    batch, sh = synth.make_batch(8, 4, config=3, variant=0, seed=61)
+    db = solver.upload(batch)
+    o = solver.solve(db, sh, keep_multipliers=True)
+    ctx = solver.ctx
+    sd = torch.zeros((1, 8, 20), dtype=torch.float64, device=d)
+    cdot = torch.zeros((MAX_TANGENTS + 1, 8, 48), dtype=torch.float64, device=d)
+    big = torch.zeros((MAX_TANGENTS + 1, 8, 20), dtype=torch.float64, device=d)
+    base = [db.seg, None, db.init, db.ref_end, db.dl_bounds, o["ctrl"], o["lam"], o["status"]]
+    sets, S, T, kw, pat = [sh], 4, 1, dict(shared_dot=sd, ctrl_dot=cdot), None
+    if case == "seg_stride":
+        z = torch.zeros(8 * 12 * 65, dtype=torch.float64, device=d)
+        base = [z, None, db.init, db.ref_end, db.dl_bounds, z, z, o["status"]]
+        S, pat = 65, "BTRAPZ_MAX_SEGMENTS"
+    elif case in ("ctrl", "lam", "status"):
+        base[{"ctrl": 5, "lam": 6, "status": 7}[case]] = None
+        pat = "needs the solve's ctrl, lam"
+    elif case == "outputs":
+        kw, pat = dict(shared_dot=sd), "both NULL"
+    elif case == "tangents":
+        kw, pat = dict(ctrl_dot=cdot), "all NULL"
+    elif case == "T_zero":
+        T, pat = 0, "BTRAPZ_MAX_TANGENTS"
+    elif case == "T_above_cap":
+        T, kw, pat = MAX_TANGENTS + 1, dict(shared_dot=big, ctrl_dot=cdot), "BTRAPZ_MAX_TANGENTS"
+    elif case == "variant":
+        sets, pat = [sh, synth.shared_params(1)], "same variant and delta"
+    elif case == "delta":
+        sets, pat = [sh, dataclasses.replace(sh, delta=2.0 * sh.delta)], "same variant and delta"
+    with pytest.raises(BtrapzError, match=pat) as e:
+        ctx.solve_jvp_device(8, S, sets, None, *base, T, **kw)
+    assert "(-1)" in str(e.value), str(e.value)
+
+
+def test_the_tangent_cap_itself_is_served(solver):
+    d = solver.device
+    batch, sh = synth.make_batch(8, 4, config=3, variant=0, seed=61)
+    db = solver.upload(batch)
+    o = solver.solve(db, sh, keep_multipliers=True)
+    big = torch.randn((MAX_TANGENTS, 8, 20), dtype=torch.float64, device=d)
+    j = solver.solve_jvp(db, sh, o, {"shared": big})
+    j1 = solver.solve_jvp(db, sh, o, {"shared": big[-1:].contiguous()})
+    assert torch.equal(j["ctrl"][-1], j1["ctrl"][0]) and torch.equal(j["cost"][-1], j1["cost"][0])
+
+
+def test_dl_bounds_tangent_on_active_rows(solver):
+    """The l axis' velocity bounds, which hardly a candidate of the other tests' batches reaches: scenario_1 with dl_bounds
+    of +-0.5, where the oracle finds l-velocity rows active in every candidate.  The adjoint identity against the VJP
+    (whose dl_bounds gradients test_gpu_vjp.py holds to its yardstick) on every solved candidate at 1e-4, with tangents in
+    dl_bounds alone and in all arrays; and far bounds among tight ones: a tangent on a far bound changes nothing, bit
+    for bit, while the tangents on the tight ones do.  (No yardstick comparison here: with the velocity at its bound
+    over whole segments the active rows are linearly dependent on the position and acceleration rows, the tangent KKT
+    system of tests/jvp_reference.py is inconsistent for a dl_bounds direction -- Tangent.consistent is False for every
+    candidate at +-0.5 to +-1.6 -- and there is no reference value to compare with.)"""
+    S, Bn = 10, 64
+    d = solver.device
+    batch, sh = synth.make_scenario1_batch(Bn, S, 0, seed=91)
+    batch.dl_bounds[:, 0::2] = -0.5; batch.dl_bounds[:, 1::2] = 0.5
+    db, o = _solve(solver, batch, sh)
+    rng = np.random.default_rng(9)
+    solved0 = (o["status"] == 1) | (o["status"] == 2)
+    jd = solver.solve_jvp(db, sh, o, _dev(solver, {"dl_bounds": rng.standard_normal((1, Bn, 10))}))
+    moved_frac = float((jd["ctrl"][0, solved0].abs().amax(1) > 1e-6).double().mean())
+    print("dl_bounds tangent alone moves %.0f %% of the solved candidates" % (100 * moved_frac))
+    assert moved_frac >= 0.5
+    worst = _identity(solver, db, sh, o, None, S, seed=6, keys=("dl_bounds",))
+    print("dl_bounds adjoint identity, dl_bounds tangents alone: worst %.3e" % worst)
+    assert worst <= 1e-4
+    worst = _identity(solver, db, sh, o, None, S, seed=5)
+    print("dl_bounds adjoint identity: worst %.3e" % worst)
+    assert worst <= 1e-4
+    # far bounds among tight ones (the bounds of point 1 at -+1e10)
+    far = L.Batch(B=Bn, S=S, seg=batch.seg.copy(), init=batch.init.copy(), ref_end=batch.ref_end.copy(), dl_bounds=batch.dl_bounds.copy())
+    far.dl_bounds[:, 2] = -1e10; far.dl_bounds[:, 3] = 1e10
+    dbf, of = _solve(solver, far, sh)
+    t1 = {"dl_bounds": rng.standard_normal((1, Bn, 10))}
+    t2 = {"dl_bounds": t1["dl_bounds"].copy()}; t2["dl_bounds"][:, :, 2:4] = 0.0
+    t3 = {"dl_bounds": np.zeros((1, Bn, 10))}; t3["dl_bounds"][:, :, 2:4] = t1["dl_bounds"][:, :, 2:4]
+    j1, j2, j3 = (solver.solve_jvp(dbf, sh, of, _dev(solver, t)) for t in (t1, t2, t3))
+    assert torch.equal(j1["ctrl"], j2["ctrl"]) and torch.equal(j1["cost"], j2["cost"])
+    assert (j3["ctrl"] == 0).all() and (j3["cost"] == 0).all()
+    solved = (of["status"] == 1) | (of["status"] == 2)
+    assert (j1["ctrl"][0, solved] != 0).any()   # (tight ones are active: their tangents do move candidates)
+
+
+def test_lm_fit_survives_a_start_that_is_never_solved(solver, monkeypatch):
+    """A start whose solve fails (its status forced to -3 at every solve) keeps an infinite loss and takes no step; the
+    other starts fit as they do without it."""
+    from test_gpu_states import GOLD, W
+    from spectral_amd import knots
+    kb = knots.parse_corridor_file(os.path.join(GOLD, "inputs", "c1.txt"))
+    rec = tune.replicated_record(solver, kb, 0, 1)
+    o = solver.solve_sets_ragged(rec, [tune.shared_of(W, kb.header, kb.delta, 0)], torch.zeros(1, dtype=torch.int32, device=solver.device))
+    with torch.no_grad():
+        target, npts = diff.sample(o["ctrl"], rec["seg"], rec["init"], solver, seg_count=rec["seg_count"], delta=kb.delta)
+    target = target[0, :, :int(npts[0])].cpu().numpy()
+    ref = tune.fit_trajectory_lm(solver, kb, 0, target, W, starts=8, steps=6, seed=6)
+    real = diff.solve_kept
+
+    def failing(*a, **k):
+        out = real(*a, **k)
+        out["status"][2] = -3
+        return out
+    monkeypatch.setattr(diff, "solve_kept", failing)
+    r = tune.fit_trajectory_lm(solver, kb, 0, target, W, starts=8, steps=6, seed=6)
+    assert np.isinf(r["losses"][2]) and r["accepted"][2] == 0
+    keep = [i for i in range(8) if i != 2]
+    assert np.allclose(r["losses"][keep], ref["losses"][keep], rtol=1e-6, atol=0) and np.isfinite(r["final_mean"])
+    assert np.allclose(r["weights"][keep], ref["weights"][keep], rtol=1e-6, atol=0)
+
+
+def test_lm_fit_against_the_adam_fit_of_the_same_run(solver):
+    """tune.fit_trajectory_lm against the unchanged tune.fit_trajectory (settings of profiles/fit_trajectory.json) on the
+    synthetic target of test_gpu_states.py::synthetic_fit, same starts: LM's final mean loss no larger than Adam's, and
+    LM's work -- every candidate of every solve launch and of every JVP launch counted once -- no larger than Adam's
+    solves."""
+    from test_gpu_states import GOLD, W, synthetic_fit
+    from spectral_amd import knots
+    prof = json.load(open(os.path.join(os.path.dirname(GOLD), "..", "profiles", "fit_trajectory.json")))["synthetic"]
+    adam, _ = synthetic_fit(solver, starts=prof["starts"], steps=prof["steps"])
+    kb = knots.parse_corridor_file(os.path.join(GOLD, "inputs", "c1.txt"))
+    rec = tune.replicated_record(solver, kb, 0, 1)
+    o = solver.solve_sets_ragged(rec, [tune.shared_of(W, kb.header, kb.delta, 0)], torch.zeros(1, dtype=torch.int32, device=solver.device))
+    with torch.no_grad():
+        target, npts = diff.sample(o["ctrl"], rec["seg"], rec["init"], solver, seg_count=rec["seg_count"], delta=kb.delta)
+    target = target[0, :, :int(npts[0])].cpu().numpy()
+    lm = tune.fit_trajectory_lm(solver, kb, 0, target, W, starts=prof["starts"], seed=6, spread=float(np.log(1.3)))
+    work = lm["solves"] + prof["starts"] * lm["jvp_launches"]
+    print("Adam: mean loss %.4e -> %.4e, %d solves; LM: %.4e -> %.4e, best %.4e, work %d (%d solves + %d JVP launches x %d)" %
+          (adam["start_mean"], adam["final_mean"], adam["solves"], lm["start_mean"], lm["final_mean"], lm["best"], work,
+           lm["solves"], lm["jvp_launches"], prof["starts"]))
+    print("LM per-step mean losses: " + " ".join("%.3e" % m for m in lm["means"]))
+    print("LM accepted steps per start: %s" % lm["accepted"].tolist())
+    assert abs(lm["start_mean"] - adam["start_mean"]) <= 1e-9 * adam["start_mean"]   # the same starts
+    assert lm["final_mean"] <= adam["final_mean"], (lm["final_mean"], adam["final_mean"])
+    assert work <= adam["solves"], (work, adam["solves"])
