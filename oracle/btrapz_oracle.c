@@ -222,6 +222,9 @@ static int cube_same(const orc_cube *a, const orc_cube *b) { /* solve_3d.cc:621 
          a->upp_skew == b->upp_skew && a->beg_l == b->beg_l && a->end_l == b->end_l;
 }
 
+static int g_stable_sort = 0;
+int orc_set_stable_sort(int on) { const int was = g_stable_sort; g_stable_sort = on ? 1 : 0; return was; }
+
 int orc_collision_check(int variant, int N, double delta, const orc_cube *cubes_in,
                         const int *counts, int num_obs, const double *x_ref,
                         const double *y_ref, orc_cube *temp, int cap) {
@@ -292,13 +295,20 @@ int orc_collision_check(int variant, int N, double delta, const orc_cube *cubes_
   }
 
   if (variant == ORC_TRAPEZOID) {
-    /* std::sort by beg_t (:630).  libstdc++ uses a stable insertion sort for
-     * n <= 16; insertion sort is used here for all n (ties keep their order). */
-    for (int i = 1; i < nt; i++) {
-      orc_cube v = temp[i];
-      int j = i - 1;
-      while (j >= 0 && v.beg_t < temp[j].beg_t) { temp[j + 1] = temp[j]; j--; }
-      temp[j + 1] = v;
+    /* std::sort by beg_t (:630).  std::sort is NOT stable: libstdc++'s introsort keeps tied keys in input order
+     * only up to 16 elements.  The order is therefore not restated here: the C++ library's own std::sort is
+     * called on (beg_t, index) pairs (std_sort_order.cpp) and the cubes follow its permutation.
+     * orc_set_stable_sort(1) swaps in std::stable_sort -- ties in input order for every n -- which the tests use
+     * to count the inputs whose corridor depends on the tie order. */
+    {
+      int *keys = (int *)malloc((size_t)nt * 2 * sizeof(int)), *perm = keys + nt;
+      orc_cube *sorted = (orc_cube *)malloc((size_t)nt * sizeof(orc_cube));
+      for (int i = 0; i < nt; i++) keys[i] = temp[i].beg_t;
+      if (g_stable_sort) orc_stable_sort_order(keys, nt, perm); else orc_std_sort_order(keys, nt, perm);
+      for (int i = 0; i < nt; i++) sorted[i] = temp[perm[i]];
+      memcpy(temp, sorted, (size_t)nt * sizeof(orc_cube));
+      free(sorted);
+      free(keys);
     }
     /* reorder for l-continuity: :639-673 */
     for (int i = 0; i < nt - 1; i++) {

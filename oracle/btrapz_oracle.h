@@ -91,6 +91,17 @@ int orc_collision_check(int variant, int N, double delta, const orc_cube *cubes,
                         const int *counts, int num_obs, const double *x_ref,
                         const double *y_ref, orc_cube *out, int cap);
 
+/* The trapezoid variant's sort of the selected cubes (solve_3d.cc:630) is the C++ library's own std::sort
+ * (std_sort_order.cpp): perm[r] = index of the key that ends at position r, the comparator sees beg_t only.
+ * orc_set_stable_sort(1) makes orc_collision_check use std::stable_sort instead (ties in input order for every n;
+ * process-wide, for counting order-sensitive inputs in tests; returns the previous setting).
+ * orc_std_sort_adversary: a key array that drives this std::sort into its heap-sort fallback (McIlroy's adversary);
+ * returns the number of comparisons it made. */
+void orc_std_sort_order(const int *beg_t, int n, int *perm);
+void orc_stable_sort_order(const int *beg_t, int n, int *perm);
+int orc_set_stable_sort(int on);
+long orc_std_sort_adversary(int n, int *keys);
+
 /* Assembly ----------------------------------------------------------------*/
 typedef struct {
   /* weights (Params) */

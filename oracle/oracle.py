@@ -86,10 +86,16 @@ class Info(C.Structure):
                 ("dua_res", C.c_double), ("rho", C.c_double)]
 
 
+_SOURCES = ("btrapz_oracle.c", "btrapz_oracle.h", "std_sort_order.cpp", "Makefile")
+
+
+def _sources_mtime():
+    return max(os.path.getmtime(os.path.join(_HERE, f)) for f in _SOURCES)
+
+
 def build(force=False):
     """Compile the oracle (building the checker is not using it)."""
-    src = os.path.join(_HERE, "btrapz_oracle.c")
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < os.path.getmtime(src):
+    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < _sources_mtime():
         subprocess.check_call(["make", "-C", _HERE, "libbtrapz_oracle.so"],
                               stdout=subprocess.DEVNULL)
     return _LIB
@@ -146,6 +152,14 @@ def lib():
             [C.POINTER(Settings), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
              C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.orc_batch_solve.restype = C.c_int
+        L.orc_std_sort_order.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+        L.orc_std_sort_order.restype = None
+        L.orc_stable_sort_order.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+        L.orc_stable_sort_order.restype = None
+        L.orc_set_stable_sort.argtypes = [C.c_int]
+        L.orc_set_stable_sort.restype = C.c_int
+        L.orc_std_sort_adversary.argtypes = [C.c_int, C.POINTER(C.c_int)]
+        L.orc_std_sort_adversary.restype = C.c_long
         _bind_mt(L)
         _lib = L
     return _lib
@@ -179,7 +193,7 @@ def _fast_path():
 
 
 def _fast_current(path):
-    return os.path.exists(path) and os.path.getmtime(path) >= os.path.getmtime(os.path.join(_HERE, "btrapz_oracle.c"))
+    return os.path.exists(path) and os.path.getmtime(path) >= _sources_mtime()
 
 
 def build_fast():
@@ -282,6 +296,35 @@ def collision_check(variant, N, delta, cube_lists, x_ref, y_ref, cap=4096):
     n = lib().orc_collision_check(variant, N, delta, arr, counts, len(cube_lists), _dp(x_ref),
                                   _dp(y_ref), out, cap)
     return n, [out[i] for i in range(max(n, 0))]
+
+
+def std_sort_order(beg_t, stable=False):
+    """The permutation the C++ library's std::sort (stable: std::stable_sort) leaves on keys compared by value alone:
+    perm[r] = index of the key at position r (src/solve_3d.cc:630; oracle/std_sort_order.cpp)."""
+    keys = np.ascontiguousarray(beg_t, dtype=np.int32)
+    perm = np.zeros(len(keys), dtype=np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    (lib().orc_stable_sort_order if stable else lib().orc_std_sort_order)(ip(keys), len(keys), ip(perm))
+    return perm
+
+
+def std_sort_adversary(n):
+    """A key array of length n on which this C++ library's std::sort runs out of its depth limit and falls back to
+    heap sort (McIlroy's adversary, run against the live std::sort)."""
+    keys = np.zeros(n, dtype=np.int32)
+    lib().orc_std_sort_adversary(n, keys.ctypes.data_as(C.POINTER(C.c_int)))
+    return keys
+
+
+class stable_sort:
+    """with O.stable_sort(): collision_check orders tied cubes as a STABLE sort would -- not the reference's order for
+    more than 16 cubes; only for counting how many inputs depend on the tie order."""
+
+    def __enter__(self):
+        self.was = lib().orc_set_stable_sort(1)
+
+    def __exit__(self, *exc):
+        lib().orc_set_stable_sort(self.was)
 
 
 def pipeline(variant, inp):

@@ -217,13 +217,143 @@ BTRAPZ_HD int dedup_segments_core(Seg *v, int n) {
     }
   return n;
 }
-BTRAPZ_HD void sort_segments_core(Seg *v, int n) {  // stable insertion sort by beg_t (libstdc++'s behaviour for n <= 16)
-  for (int i = 1; i < n; i++) {
-    const Seg x = v[i];
-    int j = i - 1;
-    while (j >= 0 && x.beg_t < v[j].beg_t) { v[j + 1] = v[j]; j--; }
-    v[j + 1] = x;
+// ---- The order of the reference's std::sort (solve_3d.cc:630: comparator on beg_t alone).  std::sort is not stable: two
+// segments that open at the same knot end in whatever order the algorithm leaves them, and the order decides the corridor
+// (reorder and overlap below see it).  The reference is built against libstdc++, whose std::sort is this introsort
+// (bits/stl_algo.h, unchanged from GCC 4 to 13): median of (first + 1, middle, last - 1) swapped to the front, an unguarded
+// Hoare partition around it, the right part first, ranges of 16 or fewer left alone, heap sort when 2 floor(lg n) levels
+// are used up, and one final insertion pass -- guarded on the first 16 elements, unguarded behind them.  Restated here
+// comparison by comparison and move by move in plain C++ (no library on the device): only `key(a) < key(b)` on integers
+// decides anything, so the permutation is the library's for every input.  Up to 16 elements the whole of it is the guarded
+// insertion pass, which keeps ties in input order.
+// T: what is moved (a Seg; on the device's wave-wide path a packed (beg_t, lane) pair).  Key: T -> the int compared.
+enum { STD_SORT_THRESHOLD = 16 };
+struct SegBegT { BTRAPZ_HD int operator()(const Seg &s) const { return s.beg_t; } };
+
+template <class T, class Key>
+BTRAPZ_HD void std_sort_linear_insert(T *v, int last, Key key) {  // __unguarded_linear_insert: no test for the front
+  const T val = v[last];
+  int next = last - 1;
+  while (key(val) < key(v[next])) { v[last] = v[next]; last = next; --next; }
+  v[last] = val;
+}
+template <class T, class Key>
+BTRAPZ_HD void std_sort_insertion(T *v, int first, int last, Key key) {  // __insertion_sort
+  if (first == last) return;
+  for (int i = first + 1; i != last; ++i) {
+    if (key(v[i]) < key(v[first])) {
+      const T val = v[i];
+      for (int m = i; m > first; --m) v[m] = v[m - 1];   // move_backward(first, i, i + 1)
+      v[first] = val;
+    } else {
+      std_sort_linear_insert(v, i, key);
+    }
   }
+}
+template <class T, class Key>
+BTRAPZ_HD void std_sort_adjust_heap(T *f, int hole, int len, T value, Key key) {  // __adjust_heap + __push_heap (stl_heap.h)
+  const int top = hole;
+  int child = hole;
+  while (child < (len - 1) / 2) {
+    child = 2 * (child + 1);
+    if (key(f[child]) < key(f[child - 1])) child--;
+    f[hole] = f[child];
+    hole = child;
+  }
+  if ((len & 1) == 0 && child == (len - 2) / 2) {
+    child = 2 * (child + 1);
+    f[hole] = f[child - 1];
+    hole = child - 1;
+  }
+  int parent = (hole - 1) / 2;
+  while (hole > top && key(f[parent]) < key(value)) { f[hole] = f[parent]; hole = parent; parent = (hole - 1) / 2; }
+  f[hole] = value;
+}
+template <class T, class Key>
+BTRAPZ_HD void std_sort_heap_sort(T *f, int len, Key key) {  // __partial_sort(first, last, last): __make_heap, __sort_heap
+  if (len < 2) return;
+  for (int parent = (len - 2) / 2;; parent--) {
+    const T value = f[parent];
+    std_sort_adjust_heap(f, parent, len, value, key);
+    if (parent == 0) break;
+  }
+  for (int last = len; last > 1;) {   // __pop_heap(first, last, last)
+    --last;
+    const T value = f[last];
+    f[last] = f[0];
+    std_sort_adjust_heap(f, 0, last, value, key);
+  }
+}
+template <class T, class Key>
+BTRAPZ_HD int std_sort_partition_pivot(T *v, int first, int last, Key key) {  // __unguarded_partition_pivot
+  const int mid = first + (last - first) / 2;
+  {  // __move_median_to_first(first, first + 1, mid, last - 1)
+    const int a = first + 1, b = mid, c = last - 1;
+    int m;
+    if (key(v[a]) < key(v[b])) m = key(v[b]) < key(v[c]) ? b : (key(v[a]) < key(v[c]) ? c : a);
+    else m = key(v[a]) < key(v[c]) ? a : (key(v[b]) < key(v[c]) ? c : b);
+    const T x = v[first]; v[first] = v[m]; v[m] = x;
+  }
+  int lo = first + 1, hi = last;  // __unguarded_partition(first + 1, last, pivot = first)
+  for (;;) {
+    while (key(v[lo]) < key(v[first])) ++lo;
+    --hi;
+    while (key(v[first]) < key(v[hi])) --hi;
+    if (!(lo < hi)) return lo;
+    const T x = v[lo]; v[lo] = v[hi]; v[hi] = x;
+    ++lo;
+  }
+}
+BTRAPZ_HD int std_sort_depth_limit(int n) {  // 2 * __lg(n)
+  int lg = 0;
+  while ((n >> (lg + 1)) > 0) lg++;
+  return 2 * lg;
+}
+// frames: room for 3 * std_sort_depth_limit(n) ints -- the (first, cut, depth) of every __introsort_loop call that waits
+// for its recursive call on the right part to return (the recursion spelled out: no call stack on the device).
+// Returns true when some range ran out of its depth limit and was heap-sorted.
+template <class T, class Key>
+BTRAPZ_HD bool std_sort_core(T *v, int n, Key key, int *frames) {
+  bool heap_sorted = false;
+  if (n <= 0) return false;
+  int first = 0, last = n, depth = std_sort_depth_limit(n), sp = 0;
+  for (;;) {   // __introsort_loop
+    if (last - first > STD_SORT_THRESHOLD) {
+      if (depth != 0) {
+        --depth;
+        const int cut = std_sort_partition_pivot(v, first, last, key);
+        frames[3 * sp] = first; frames[3 * sp + 1] = cut; frames[3 * sp + 2] = depth; sp++;   // the caller goes on with [first, cut)
+        first = cut;                                                                          // ... after [cut, last)
+        continue;
+      }
+      std_sort_heap_sort(v + first, last - first, key);
+      heap_sorted = true;
+    }
+    if (sp == 0) break;
+    sp--;
+    first = frames[3 * sp]; last = frames[3 * sp + 1]; depth = frames[3 * sp + 2];
+  }
+  if (n > STD_SORT_THRESHOLD) {   // __final_insertion_sort
+    std_sort_insertion(v, 0, (int)STD_SORT_THRESHOLD, key);
+    for (int i = STD_SORT_THRESHOLD; i != n; ++i) std_sort_linear_insert(v, i, key);
+  } else {
+    std_sort_insertion(v, 0, n, key);
+  }
+  return heap_sorted;
+}
+// Returns whether the heap-sort fallback ran (a fact about the input the tests ask for).
+BTRAPZ_HD bool sort_segments_core(Seg *v, int n) {
+  if (n <= STD_SORT_THRESHOLD) {  // the guarded insertion pass alone: a stable insertion sort by beg_t
+    for (int i = 1; i < n; i++) {
+      const Seg x = v[i];
+      int j = i - 1;
+      while (j >= 0 && x.beg_t < v[j].beg_t) { v[j + 1] = v[j]; j--; }
+      v[j + 1] = x;
+    }
+    return false;
+  }
+  int frames[3 * 2 * 31];
+  return std_sort_core(v, n, SegBegT(), frames);
 }
 // Trapezoid variant, first half: pull a segment that continues segment i's lane next to it (solve_3d.cc:640-666).
 // Only beg_l, beg_t and end_t are compared; the device runs the k search across the lanes (corridor_kernels.hip).

@@ -5,7 +5,7 @@
 // obstacle -> slopes (all lanes, loads issued in blocks) -> CorridorGeneration + CorridorSplit (ballot search for the
 // next slope break, then one lane per base segment; extract_segments_wave) -> CollisionCheck: one lane per segment
 // counts the reference knots inside it, a scan turns the reference's running counter into a per-segment decision
-// -> de-dup (keys compared through readlane), stable rank sort, the "continues this lane" reorder (ballot search) and
+// -> de-dup (keys compared through readlane), rank sort in std::sort's order (corridor_core.h), the "continues this lane" reorder (ballot search) and
 // the neighbour-overlap walk, all on keys held in the lanes (only the cuboid variant's all-pairs overlap pass runs
 // serially) -> the batch record of the QP kernel (one lane per selected segment, coalesced field-major stores).
 // The serial statements of corridor_core.h (what the host driver runs) remain the fallback for the shapes the
@@ -326,7 +326,7 @@ __device__ __forceinline__ void corridor_candidate(const CorridorArgs &a, int st
   const size_t shared_doubles = staged && O > 2 ? (size_t)O * N * 2 : (size_t)N * 4;
   int *hits = reinterpret_cast<int *>(dyn + shared_doubles);   // reference knots inside every segment
   int *ocount = hits + cap_all;
-  int *key = ocount + 64;                                // beg_t of the survivors of the de-dup, for the rank sort
+  int *key = ocount + 64;                                // (beg_t, lane) of the survivors of the de-dup, when more than 16 of them tie
   short *slot_of = reinterpret_cast<short *>(key + cap_sel);  // flattened segment index -> slot in all[]
   short *pick = slot_of + cap_all;                       // slots of the selected segments, in selection order
   PrismBounds prism;
@@ -543,7 +543,7 @@ __device__ __forceinline__ void corridor_candidate(const CorridorArgs &a, int st
   __syncthreads();
   if (overflow && a.pass == 0 && a.retry_list && lane == 0) a.retry_list[atomicAdd(a.retry_count, 1)] = b;  // second chance
   CABL_MARK(5, "DEDUP");
-  // ---- de-dup (keep first), stable sort by beg_t: lane j holds selected segment j ----
+  // ---- de-dup (keep first), the reference's std::sort by beg_t: lane j holds selected segment j ----
   int S = overflow ? -1 : 0;
   if (!overflow && nsel > 0) {
 #ifdef CABL_NOORDER
@@ -590,16 +590,39 @@ __device__ __forceinline__ void corridor_candidate(const CorridorArgs &a, int st
     const unsigned long long kept = __ballot(keep);
     const int pos = __popcll(kept & ((1ull << lane) - 1ull)), n = __popcll(kept);
     int rank = pos;
-    // (round 6) nothing dropped and the first knots already in non-decreasing order along the lanes -- a corridor selected
-    // obstacle by obstacle in the order the reference passes them --: the stable rank IS the lane
+    // The reference's std::sort (sort_segments_core, corridor_core.h) keeps tied first knots in input order only up to 16
+    // segments: the stable rank below is its order for n <= 16, and for any n when no two kept segments share a first knot
+    // (distinct keys have one sorted order).
+    // (round 6) nothing dropped and the first knots already in order along the lanes -- a corridor selected obstacle by
+    // obstacle in the order the reference passes them --: the rank IS the lane.  Non-decreasing will do up to 16 segments;
+    // beyond, std::sort moves tied segments of a sorted list too, and only strictly increasing first knots leave it alone.
+    const bool big = n > STD_SORT_THRESHOLD;                // wave-uniform
     const int bt_below = __builtin_amdgcn_update_dpp(0, mine.beg_t, 0x138, 0xf, 0xf, false);   // wave_shr:1: lane l - 1's
-    const bool in_order = n == nsel && __ballot(lane > 0 && lane < nsel && bt_below > mine.beg_t) == 0;
+    const bool in_order = n == nsel && __ballot(lane > 0 && lane < nsel && (big ? bt_below >= mine.beg_t : bt_below > mine.beg_t)) == 0;
     if (a.variant == 0 && !in_order) {  // stable rank by beg_t among the kept ones
       rank = 0;
+      bool tied = false;
       for (int i = 0; i < nsel; i++) {
         if (!((kept >> i) & 1ull)) continue;
         const int bt_i = __builtin_amdgcn_readlane(mine.beg_t, i);
         rank += (bt_i < mine.beg_t || (bt_i == mine.beg_t && i < lane)) ? 1 : 0;
+        tied = tied || (bt_i == mine.beg_t && i != lane);
+      }
+      if (big && __ballot(keep && tied) != 0) {
+        // More than 16 segments and a tie: the library's order, statement by statement, by ONE lane (std_sort_core; at most 64
+        // keys, a few hundred integer comparisons) on (beg_t, lane) pairs packed into key[] -- first knots are knots of the
+        // horizon, below 2^25 -- in the order of the kept segments; its frames in ocount[] (read for the last time by the
+        // selection; 3 * 2 * lg 64 = 36 of its 64 ints).  Then position r knows its lane, and every lane is told its position.
+        struct PairBegT { BTRAPZ_HD int operator()(int p) const { return p >> 6; } };
+        if (keep) key[pos] = (mine.beg_t << 6) | lane;
+        __syncthreads();
+        if (lane == 0) std_sort_core(key, n, PairBegT(), ocount);
+        __syncthreads();
+        const int from = lane < n ? key[lane] & 63 : 0;
+        __syncthreads();
+        if (lane < n) key[from] = lane;
+        __syncthreads();
+        if (keep) rank = key[lane];
       }
     }
     __syncthreads();                                       // every lane has its copy: all[] may be overwritten

@@ -9,6 +9,8 @@
 //   host_check text <seed> <count>                   -> parse_double / format_3 against strtod / snprintf
 //   host_check prisms <seed> <scenes>                -> strips of seeded scenes, one line per strip and knot sample
 //   host_check knots <seed> <count>                  -> knot_inside_own_span against knot_inside under its preconditions
+//   host_check sort <file>                           -> sort_segments_core on key arrays ("n k0 .. kn-1" per line): per array
+//                                                       "<heap-sort fallback taken> p0 .. pn-1", p[r] = input index at position r
 #include "simt_shim.h"
 
 #include <cstdio>
@@ -175,7 +177,27 @@ static int run_knots(unsigned seed, int count) {
   return bad ? 1 : 0;
 }
 
+// sort_segments_core (corridor_core.h: the restatement of the order std::sort gives the selected segments) on key arrays
+// read from a file; every segment carries its input index, so the output is the permutation.  Exact-size heap blocks: a
+// read or write outside [0, n) -- the unguarded loops rely on a smaller element in front -- is the sanitizer's to find.
+static int run_sort(const char *path) {
+  FILE *f = fopen(path, "r");
+  if (!f) return 2;
+  int n;
+  while (fscanf(f, "%d", &n) == 1 && n >= 0) {
+    std::vector<Seg> v((size_t)n, seg_default());
+    for (int i = 0; i < n; i++) { if (fscanf(f, "%d", &v[(size_t)i].beg_t) != 1) { fclose(f); return 2; } v[(size_t)i].count = i; }
+    const bool heap = sort_segments_core(v.data(), n);
+    printf("%d", heap ? 1 : 0);
+    for (int i = 0; i < n; i++) printf(" %d", v[(size_t)i].count);
+    printf("\n");
+  }
+  fclose(f);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 3 && !strcmp(argv[1], "sort")) return run_sort(argv[2]);
   if (argc >= 4 && !strcmp(argv[1], "knots")) return run_knots((unsigned)atoi(argv[2]), atoi(argv[3]));
   if (argc >= 4 && !strcmp(argv[1], "corridor")) return run_corridor(atoi(argv[2]), argv[3], argc > 4 ? argv[4] : nullptr);
   if (argc >= 4 && !strcmp(argv[1], "text")) return run_text((unsigned)atoi(argv[2]), atoi(argv[3]));

@@ -113,3 +113,140 @@ def oracle_corridor(kb, b, variant, per_obstacle_cap=None):
     if per_obstacle_cap is not None and max(len(l) for l in lists) > per_obstacle_cap:
         return None, None
     return O.collision_check(variant, kb.N, kb.delta, lists, kb.s_ref[b], kb.l_ref[b])
+
+
+def tied_lanes_knot_batch(seed, B, N, lanes=2, n_range=(17, 26), max_breaks=6):
+    """Corridor-stage inputs on which the ORDER of tied segments matters: `lanes` lane obstacles whose s bounds kink at the
+    SAME knots (per candidate: a random set of knots, at least three apart), so that their segments -- and the one-second
+    pieces CorridorSplit cuts them into -- open at the same knots, lane for lane.  The lanes are nested in l (lane o spans
+    [o, lanes + 1]) and the reference's l steps between the levels o + 0.5: where it runs at level o it is inside lanes 0..o,
+    and the selection takes the tied segments of all of them; lane 0 holds the reference throughout.  How long the reference
+    stays at the upper levels is drawn per candidate so that the number of selected segments spreads over about n_range --
+    never one fixed n: std::sort and a stable sort agree for some n and not for others.  The lanes differ in beg_l, so the
+    de-dup drops nothing.  Everything is finite and well formed: this family is about the order alone."""
+    from spectral_amd import synth
+    from spectral_amd.knots import KnotBatch
+    rng = np.random.default_rng(seed)
+    delta = 0.1
+    tt = np.arange(N) * delta
+    sb = np.zeros((B, lanes, N, 2)); lb = np.zeros((B, lanes, N, 2))
+    s_ref = np.zeros((B, N)); l_ref = np.zeros((B, N))
+    for b in range(B):
+        v = rng.uniform(4.0, 8.0)
+        s_ref[b] = v * tt
+        kinks = []
+        for k in sorted(rng.choice(np.arange(3, N - 3), size=int(rng.integers(0, max_breaks + 1)), replace=False).tolist()):
+            if not kinks or k - kinks[-1] >= 3:
+                kinks.append(int(k))
+        edges = [0] + kinks + [N - 1]
+        for o in range(lanes):
+            d = np.zeros(N); d[0] = rng.uniform(4.0, 8.0)
+            sign = 1.0 if rng.random() < 0.5 else -1.0
+            for j in range(len(edges) - 1):            # a zigzag: the slope changes by 0.6 or more at every kink (threshold 0.2)
+                k0, k1 = edges[j], edges[j + 1]
+                mag = min(rng.uniform(0.3, 1.5), max(0.3, 3.0 / ((k1 - k0) * delta)))
+                d[k0:k1 + 1] = d[k0] + sign * mag * (np.arange(k1 - k0 + 1) * delta)
+                sign = -sign
+            d += 1.0 - min(d.min(), 1.0)                # the reference stays above the lower bound ...
+            sb[b, o, :, 0] = s_ref[b] - d
+            sb[b, o, :, 1] = sb[b, o, :, 0] + d.max() + rng.uniform(5.0, 20.0)   # ... and below the upper one
+            lb[b, o, :, 0] = float(o); lb[b, o, :, 1] = float(lanes + 1)
+        # pieces per lane: one per second and one per kink, about; the upper lanes add theirs while the reference is inside
+        per_lane = (N - 1) / 10.0 + len(kinks)
+        extra = rng.uniform(n_range[0], n_range[1]) - per_lane
+        frac = min(max(extra / (per_lane * (lanes - 1)), 0.0), 1.0)
+        level = np.zeros(N, dtype=int)
+        for o in range(1, lanes):
+            span = int(round(frac * N))
+            if span > 0:
+                start = int(rng.integers(0, N - span + 1))
+                level[start:start + span] = np.maximum(level[start:start + span], o if rng.random() < 0.7 else lanes - 1)
+        l_ref[b] = level + 0.5
+    return KnotBatch(B, N, lanes, delta, sb, lb, np.tile(np.array([0.0, 20.0]), (B, N, 1)), np.tile(np.array([-3.0, 3.0]), (B, N, 1)),
+                     s_ref, l_ref, np.tile(np.array([0.0, 6.0, 0.0, 0.5, 0.0, 0.0]), (B, 1)), dict(synth.C1_HEADER))
+
+
+CUBE_ATTRS = ("beg_t", "end_t", "t", "down_bias", "down_skew", "upp_bias", "upp_skew", "l_down_bias", "l_down_skew", "l_upp_bias",
+              "l_upp_skew", "beg_l", "end_l")
+
+
+def cube_rows(cubes):
+    """The compared fields of a corridor as one array, [n, 13] (exact comparisons: np.array_equal)."""
+    return np.array([[getattr(c, a) for a in CUBE_ATTRS] for c in cubes], dtype=np.float64).reshape(len(cubes), len(CUBE_ATTRS))
+
+
+_order_cache = {}
+
+
+def oracle_corridors_both_orders(kb, key):
+    """The oracle's trapezoid corridor of every candidate of kb under std::sort (the reference's order) and under the stable
+    switch: ([(n, rows)], [(n, rows)]), computed once per `key` and shared by the tests that need it."""
+    if key not in _order_cache:
+        real = [oracle_corridor(kb, b, 0) for b in range(kb.B)]
+        with O.stable_sort():
+            stable = [oracle_corridor(kb, b, 0) for b in range(kb.B)]
+        pack = lambda res: [(n, cube_rows(c[:max(n, 0)])) for n, c in res]
+        _order_cache[key] = (pack(real), pack(stable))
+    return _order_cache[key]
+
+
+def order_sensitive(real, stable):
+    """Indices of the candidates whose final corridor differs between the two orders."""
+    return [b for b, ((n, r), (m, s)) in enumerate(zip(real, stable)) if n != m or not np.array_equal(r, s)]
+
+
+def tied_prism_scenes(seed, B, N=201, max_cars=3):
+    """The tied family for the stage that evaluates its bounds from obstacle prisms: neighbouring lateral strips share an
+    edge, and a reference that runs exactly ON that edge (membership is l >= beg_l and l <= end_l) is inside both -- their
+    one-second pieces open at the same knots.  Per candidate the reference sits on a shared edge for a window of the horizon
+    and in the strip below it before and after, so the number of selected segments spreads above (N - 1) / 10.
+    Returns (scenes, bounds, s_ref, l_ref): bounds[b] = the CPU restatement's strips [(s [N][2], l [N][2])]."""
+    from oracle import prism_oracle as P
+    rng = np.random.default_rng(seed)
+    tt = np.arange(N) * 0.1
+    scenes, bounds = [], []
+    s_ref = np.zeros((B, N)); l_ref = np.zeros((B, N))
+    for b in range(B):
+        cars = [dict(centre=(float(rng.uniform(15, 45)), float(rng.uniform(-1.0, 7.0)), 0), vel_s=float(rng.uniform(0, 3)), vel_l=0.0,
+                     time=float(rng.choice([3.0, 4.0]))) for _ in range(int(rng.integers(1, max_cars + 1)))]
+        strips = P.prism_bounds(cars, N)
+        scenes.append(cars); bounds.append(strips)
+        j = int(rng.integers(0, len(strips) - 1))                       # the edge between strips j and j + 1
+        edge = float(np.array(strips[j + 1][1])[0, 0])
+        inside = 0.5 * (float(np.array(strips[j][1])[0, 0]) + edge)
+        span = int(rng.integers(10, 70)); start = int(rng.integers(0, N - span))
+        l_ref[b] = inside; l_ref[b, start:start + span] = edge
+        s_ref[b] = rng.uniform(0.5, 1.0) + rng.uniform(0.2, 0.6) * tt   # slow: behind the cars, inside the road's s range
+    return scenes, bounds, s_ref, l_ref
+
+
+# The tied-lanes shapes of tests/test_sort_order.py (host path, B = 64) and tests/test_gpu_sort_order.py (device, B = 256):
+# name -> (seed, N, lanes, n_range, max_breaks).  Each selects one code path of the device stage (N <= 512 and at most 64
+# selected segments: the wave-wide kernel; beyond: one lane per candidate) and meets the sensitivity floor at both sizes.
+# The wave-wide kernel lists at most 160 // lanes segments per obstacle and reports a candidate that needs more as unusable
+# (seg_count = -1): a horizon of 512 knots is 52 one-second pieces per lane, so three lanes leave room for one more piece
+# per lane (53) and their bounds kink at most twice; max_obstacle_segments() is what the device test holds the batch to.
+TIED_SHAPES = {
+    "N201_2lanes": (11, 201, 2, (17, 26), 4),
+    "N512_2lanes": (12, 512, 2, (52, 62), 5),
+    "N512_3lanes": (13, 512, 3, (52, 55), 2),
+    "N700_2lanes": (14, 700, 2, (65, 120), 30),
+}
+
+
+def tied_shape_batch(name, B):
+    seed, N, lanes, n_range, max_breaks = TIED_SHAPES[name]
+    return tied_lanes_knot_batch(seed + (0 if B == 256 else 1000), B, N, lanes, n_range, max_breaks)
+
+
+def max_obstacle_segments(kb):
+    """The longest per-obstacle segment list (CorridorGeneration + CorridorSplit) of any candidate of kb."""
+    return max(len(O.corridor_generation(0, kb.N, kb.delta, kb.s_bounds[b, o], kb.l_bounds[b, o])) for b in range(kb.B) for o in range(kb.num_obs))
+
+
+def assert_sensitivity_floor(real, stable, what):
+    """A batch on which the tie order never matters checks nothing: at least 10 candidates and at least 10 % of them must get
+    another final corridor from the oracle under std::sort than under the stable switch (the oracle alone decides, on the CPU)."""
+    sens = order_sensitive(real, stable)
+    assert len(sens) >= 10 and len(sens) >= 0.1 * len(real), (what, len(sens), len(real))
+    return sens
