@@ -108,62 +108,108 @@ static_assert(offsetof(btrapz::Shared, acc_l) == offsetof(btrapz::Shared, acc_s)
               offsetof(btrapz::Shared, jerk_l) == offsetof(btrapz::Shared, acc_s) + 6 * sizeof(double), "Shared: acc_s, acc_l, jerk_s, jerk_l contiguous");
 static_assert(std::is_trivially_copyable<btrapz::KernelArgs>::value && alignof(btrapz::KernelArgs) <= 8, "KernelArgs is passed by value at kernarg offset 0");
 
+// One device allocation of a context.  Every buffer enters its context's list when it is constructed: btrapz_destroy and
+// btrapz_workspace_bytes walk that list.  grow() is what every workspace here does when a launch needs more than the
+// buffer holds: free it and allocate exactly the bytes asked for (no rounding; the contents are not kept).
+// Fatal use: GROW(c, buffer, bytes) below.  Non-fatal use (the two-launch solve's workspace, the corridor stage's lists):
+// test grow()'s result and clear HIP's error with hipGetLastError().
+struct DevBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  explicit DevBuf(std::vector<DevBuf *> &owner) { owner.push_back(this); }
+  DevBuf(const DevBuf &) = delete;
+  void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
+  __attribute__((always_inline)) hipError_t grow(size_t need) { return need <= bytes ? hipSuccess : regrow(need); }   // (the usual case: a compare)
+  __attribute__((noinline)) hipError_t regrow(size_t need) {
+    release();
+    const hipError_t e = hipMalloc(&p, need);
+    if (e == hipSuccess) bytes = need; else p = nullptr;
+    return e;
+  }
+};
+template <class T> struct Buf : DevBuf {   // ... that holds elements of T
+  using DevBuf::DevBuf;
+  T *ptr() const { return static_cast<T *>(p); }
+  operator T *() const { return ptr(); }
+  size_t cap() const { return bytes / sizeof(T); }
+};
+// Arrays that move together under one capacity (read off the one allocated LAST): all are released before any is
+// allocated, so an allocation that fails half-way leaves the last one empty and the next call starts over.
+template <class... B> static void release_all(B &...b) { (b.release(), ...); }
+
 struct btrapz_ctx {
   int device = 0;
   std::string err;
-  // workspace (grown on demand)
-  double *d_axis_obj = nullptr;
-  int *d_axis_status = nullptr, *d_axis_iters = nullptr;
-  double *d_axis_viol = nullptr;    // [2B][4] rescue pass: row violations per class
+  std::vector<DevBuf *> bufs;       // every device buffer below (declared first: the buffers register here)
+  // workspace (grown on demand): per-axis records of the last solve; one capacity, d_axis_iters is allocated last
+  Buf<double> d_axis_obj{bufs};
+  Buf<double> d_axis_viol{bufs};    // [2B][4] rescue pass: row violations per class
+  Buf<int> d_axis_status{bufs}, d_axis_iters{bufs};
   size_t viol_valid = 0;            // candidates of the last solve with a rescue pass (0: none)
-  size_t axis_cap = 0;
-  double *d_mqm = nullptr;          // [2][4][21]
+  Buf<double> d_mqm{bufs};          // [2][4][21]
   double h_mqm_w[8] = {NAN, NAN, NAN, NAN, NAN, NAN, NAN, NAN};  // weights the table was built for
   // ragged batches: candidate order by segment count + bucket tables
-  int *d_order = nullptr; size_t order_cap = 0;
-  int *d_meta = nullptr;            // [198] histogram/cand_prefix, wave_prefix, cursors
-  int *d_retry = nullptr; size_t retry_cap = 0;   // corridor stage: [0] count, [1..] candidates of the retry pass
-  void *d_strips = nullptr; size_t strip_cap = 0; // btrapz_prism_corridor_batch_device's two-launch path: the strips
-  void *d_corr_ws = nullptr; size_t corr_ws_cap = 0;   // corridor_serial_kernel's segment lists (horizons beyond the wave-wide kernels)
-  int *d_long_list = nullptr; size_t long_list_cap = 0;   // ragged batches: the candidates of more than 64 segments, by count
-  // rescue pass (btrapz_options.elastic): keys [2][B], per-axis candidate lists [2][B], bucket tables [2][198]
-  // The workspaces above serve one launch sequence at a time.  Launches of one context issued on DIFFERENT streams are
-  // ordered behind each other with this event (recorded after every sequence, waited for when the stream changes).
+  Buf<int> d_order{bufs};
+  Buf<int> d_meta{bufs};            // [198] histogram/cand_prefix, wave_prefix, cursors
+  Buf<int> d_retry{bufs};           // corridor stage: [0] count, [1..] candidates of the retry pass
+  Buf<char> d_strips{bufs};         // btrapz_prism_corridor_batch_device's two-launch path: the strips
+  Buf<char> d_corr_ws{bufs};        // corridor_serial_kernel's segment lists (horizons beyond the wave-wide kernels)
+  Buf<int> d_long_list{bufs};       // ragged batches: the candidates of more than 64 segments, by count
+  // The workspaces serve one launch sequence at a time.  Launches of one context issued on DIFFERENT streams are
+  // ordered behind each other with this event (recorded after every sequence, waited for when the stream changes: ws_open).
   hipEvent_t ws_free = nullptr; hipStream_t ws_stream = nullptr; bool ws_used = false;
-  double *d_argmin_cost = nullptr; long long *d_argmin_idx = nullptr; size_t argmin_cap = 0;   // partial arg-mins
-  int *d_rescue = nullptr; size_t rescue_cap = 0;
-  int *d_rescue_meta = nullptr;
+  Buf<double> d_argmin_cost{bufs}; Buf<long long> d_argmin_idx{bufs};   // partial arg-mins (one capacity, idx allocated last)
+  // rescue pass (btrapz_options.elastic): keys [2][B], per-axis candidate lists [2][B], bucket tables [2][198]
+  Buf<int> d_rescue{bufs};
+  Buf<int> d_rescue_meta{bufs};
   // staging for the host-pointer wrapper
-  double *d_stage = nullptr; size_t stage_cap = 0;
-  double *d_single = nullptr;       // control points of the single-candidate launch (find_traj)
+  Buf<double> d_stage{bufs};
+  Buf<int> d_istage{bufs};
+  Buf<double> d_single{bufs};       // control points of the single-candidate launch (find_traj)
   // what a warm single-candidate launch leaves for the next one: joint states [2][64][3], multipliers [2][36][64] (two
   // sets, read / written alternately), and the problem shape they belong to
-  double *d_single_warm = nullptr; int single_S = 0, single_variant = -1, single_flip = 0;
-  int *d_queue = nullptr;           // [2] candidate counters of the persistent launch (ipm_solve_queue_kernel)
+  Buf<double> d_single_warm{bufs}; int single_S = 0, single_variant = -1, single_flip = 0;
+  Buf<int> d_queue{bufs};           // [2] candidate counters of the persistent launch (ipm_solve_queue_kernel)
   // capped solve (btrapz_options.cap_iter): iterates of the suspended axis problems, their slots and list keys
-  double *d_susp_state = nullptr; size_t susp_state_doubles = 0;
-  int *d_susp_ints = nullptr; size_t susp_ints = 0;      // [count, 3 pad] [bucket tables 2 x 198] [2B keys] [2B slots]
+  Buf<double> d_susp_state{bufs};
+  Buf<int> d_susp_ints{bufs};       // [count, 3 pad] [bucket tables 2 x 198] [2B keys] [2B slots]
   int resident_waves = 1024;        // wavefronts the device holds at one per SIMD
   int last_form = -1;               // btrapz_last_solve_form
-  int *d_istage = nullptr; size_t istage_cap = 0;
   // btrapz_solve_sets_device: the device view of every set and its M'QM table, cached by content (h_sets: what the tables
   // were built from); uploads go through two pinned staging buffers used in turn, the copy out of each marked by its event
-  Shared *d_sets = nullptr; double *d_mqm_sets = nullptr; size_t sets_cap = 0;
+  Buf<Shared> d_sets{bufs}; Buf<double> d_mqm_sets{bufs}; size_t sets_cap = 0;
   std::vector<Shared> h_sets;
   Shared *h_sets_stage[2] = {nullptr, nullptr}; hipEvent_t sets_copied[2] = {nullptr, nullptr};
   bool sets_copy_pending[2] = {false, false}; int sets_stage_next = 0;
-  int *d_sets_meta = nullptr; size_t sets_meta_cap = 0;   // bucket tables of a sets batch: [n_keys + 1] x 2 + [n_keys]
-  double *d_mqm_unit = nullptr;     // btrapz_solve_vjp_device: the M'QM table with every weight 1 ([2][4][21])
+  Buf<int> d_sets_meta{bufs};       // bucket tables of a sets batch: [n_keys + 1] x 2 + [n_keys]
+  Buf<double> d_mqm_unit{bufs};     // the M'QM table with every weight 1 ([2][4][21]): the solve's VJP and JVP
 };
 
-#define HIPCHK(ctx, call)                                                                     \
+#define HIPCHK_AS(ctx, what, call)                                                            \
   do {                                                                                        \
     hipError_t e_ = (call);                                                                   \
     if (e_ != hipSuccess) {                                                                   \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
+      (ctx)->err = std::string(what) + ": " + hipGetErrorString(e_);                          \
       return BTRAPZ_EHIP;                                                                     \
     }                                                                                         \
   } while (0)
+#define HIPCHK(ctx, call) HIPCHK_AS(ctx, #call, call)
+// (a fatal grow(): its message reads as the hipMalloc call it stands for)
+#define GROW(ctx, buf, nbytes) HIPCHK_AS(ctx, "hipMalloc(&c->" #buf ", " #nbytes ")", (ctx)->buf.grow(nbytes))
+#define TRY(call) do { const int rc_ = (call); if (rc_ != BTRAPZ_OK) return rc_; } while (0)   // (a step of this file that failed)
+
+// A launch sequence on the context's workspaces: opened by waiting for the sequence before it when that ran on another
+// stream, closed by recording the event the next one waits for.  Entry points that touch no workspace do neither.
+static int ws_wait(btrapz_ctx *c, hipStream_t stream) {
+  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  return BTRAPZ_OK;
+}
+static int ws_open(btrapz_ctx *c, hipStream_t stream) { HIPCHK(c, hipSetDevice(c->device)); return ws_wait(c, stream); }
+static int ws_close(btrapz_ctx *c, hipStream_t stream) {
+  c->ws_stream = stream; c->ws_used = true;
+  HIPCHK(c, hipEventRecord(c->ws_free, stream));
+  return BTRAPZ_OK;
+}
 
 int btrapz_ctx_device(const btrapz_ctx *c) { return c ? c->device : 0; }
 
@@ -181,6 +227,8 @@ BTRAPZ_EXPORT int btrapz_build_has_experiments(void) {
 #endif
 }
 
+static void free_buffers(btrapz_ctx *c) { for (DevBuf *b : c->bufs) b->release(); }
+
 BTRAPZ_EXPORT int btrapz_create(btrapz_ctx **out, int device) {
   if (!out) return BTRAPZ_EINVAL;
   *out = nullptr;
@@ -189,13 +237,13 @@ BTRAPZ_EXPORT int btrapz_create(btrapz_ctx **out, int device) {
   if (hipSetDevice(device) != hipSuccess) return BTRAPZ_ENODEVICE;
   btrapz_ctx *c = new btrapz_ctx();
   c->device = device;
-  if (hipMalloc(&c->d_mqm, sizeof(double) * 168) != hipSuccess) { delete c; return BTRAPZ_ENOMEM; }
+  if (c->d_mqm.grow(sizeof(double) * 168) != hipSuccess) { delete c; return BTRAPZ_ENOMEM; }
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->resident_waves = 4 * cus;
   }
-  if (hipMalloc(&c->d_queue, sizeof(int) * 2) != hipSuccess) { (void)hipFree(c->d_mqm); delete c; return BTRAPZ_ENOMEM; }
-  if (hipEventCreateWithFlags(&c->ws_free, hipEventDisableTiming) != hipSuccess) { (void)hipFree(c->d_mqm); (void)hipFree(c->d_queue); delete c; return BTRAPZ_ENOMEM; }
+  if (c->d_queue.grow(sizeof(int) * 2) != hipSuccess) { free_buffers(c); delete c; return BTRAPZ_ENOMEM; }
+  if (hipEventCreateWithFlags(&c->ws_free, hipEventDisableTiming) != hipSuccess) { free_buffers(c); delete c; return BTRAPZ_ENOMEM; }
   *out = c;
   return BTRAPZ_OK;
 }
@@ -203,12 +251,7 @@ BTRAPZ_EXPORT int btrapz_create(btrapz_ctx **out, int device) {
 BTRAPZ_EXPORT int btrapz_destroy(btrapz_ctx *c) {
   if (!c) return BTRAPZ_EINVAL;
   (void)hipSetDevice(c->device);
-  (void)hipFree(c->d_axis_obj); (void)hipFree(c->d_axis_status); (void)hipFree(c->d_axis_iters); (void)hipFree(c->d_axis_viol);
-  (void)hipFree(c->d_mqm); (void)hipFree(c->d_stage); (void)hipFree(c->d_istage); (void)hipFree(c->d_single);
-  (void)hipFree(c->d_queue); (void)hipFree(c->d_single_warm); (void)hipFree(c->d_susp_state); (void)hipFree(c->d_susp_ints);
-  (void)hipFree(c->d_order); (void)hipFree(c->d_meta); (void)hipFree(c->d_retry); (void)hipFree(c->d_strips); (void)hipFree(c->d_corr_ws); (void)hipFree(c->d_long_list);
-  (void)hipFree(c->d_rescue); (void)hipFree(c->d_rescue_meta); (void)hipFree(c->d_argmin_cost); (void)hipFree(c->d_argmin_idx);
-  (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets); (void)hipFree(c->d_sets_meta); (void)hipFree(c->d_mqm_unit);
+  free_buffers(c);
   for (int i = 0; i < 2; i++) {
     if (c->sets_copy_pending[i]) (void)hipEventSynchronize(c->sets_copied[i]);
     if (c->h_sets_stage[i]) (void)hipHostFree(c->h_sets_stage[i]);
@@ -220,34 +263,25 @@ BTRAPZ_EXPORT int btrapz_destroy(btrapz_ctx *c) {
 }
 
 BTRAPZ_EXPORT const char *btrapz_last_error(const btrapz_ctx *c) { return c ? c->err.c_str() : "null context"; }
-// Device memory the context holds for its launches right now (it grows on demand and is kept): per-axis records, bucket
-// tables and lists, the hand-over workspace of the two-launch solve, staging of the host-pointer wrapper.
+// Device memory the context holds for its launches right now (it grows on demand and is kept): every device buffer of
+// the context -- per-axis records, bucket tables and lists, the hand-over workspace of the two-launch solve, the corridor
+// stage's lists, the sets' tables, staging of the host-pointer wrapper.
 BTRAPZ_EXPORT long long btrapz_workspace_bytes(const btrapz_ctx *c) {
   if (!c) return 0;
   size_t n = 0;
-  n += c->axis_cap * (sizeof(double) * 5 + sizeof(int) * 2);
-  n += sizeof(double) * 168 + sizeof(int) * 2;
-  n += c->order_cap * sizeof(int) + (c->d_meta ? 198 * sizeof(int) : 0) + c->retry_cap * sizeof(int) + c->strip_cap;
-  n += c->argmin_cap * (sizeof(double) + sizeof(long long));
-  n += c->rescue_cap * 2 * sizeof(int) + (c->d_rescue_meta ? 2 * 198 * sizeof(int) : 0);
-  n += c->stage_cap * sizeof(double) + c->istage_cap * sizeof(int);
-  n += (c->d_single ? sizeof(double) * 12 * BTRAPZ_MAX_SEGMENTS : 0) + (c->d_single_warm ? sizeof(double) * 2 * (2 * 64 * 3 + 2 * 36 * 64) : 0);
-  n += c->susp_state_doubles * sizeof(double) + c->susp_ints * sizeof(int);
-  n += c->sets_cap * (sizeof(Shared) + sizeof(double) * 168) + c->sets_meta_cap * sizeof(int);   // btrapz_solve_sets_device
+  for (const DevBuf *b : c->bufs) n += b->bytes;
   return (long long)n;
 }
 BTRAPZ_EXPORT int btrapz_last_solve_form(const btrapz_ctx *c) { return c ? c->last_form : -1; }
 
 static int ensure_axis_ws(btrapz_ctx *c, size_t nprob) {
-  if (nprob <= c->axis_cap) return BTRAPZ_OK;
-  (void)hipFree(c->d_axis_obj); (void)hipFree(c->d_axis_status); (void)hipFree(c->d_axis_iters); (void)hipFree(c->d_axis_viol);
-  c->d_axis_obj = nullptr; c->d_axis_status = nullptr; c->d_axis_iters = nullptr; c->d_axis_viol = nullptr; c->axis_cap = 0;
+  if (nprob <= c->d_axis_iters.cap()) return BTRAPZ_OK;
+  release_all(c->d_axis_obj, c->d_axis_status, c->d_axis_iters, c->d_axis_viol);
   c->viol_valid = 0;
-  HIPCHK(c, hipMalloc(&c->d_axis_obj, sizeof(double) * nprob));
-  HIPCHK(c, hipMalloc(&c->d_axis_viol, sizeof(double) * 4 * nprob));
-  HIPCHK(c, hipMalloc(&c->d_axis_status, sizeof(int) * nprob));
-  HIPCHK(c, hipMalloc(&c->d_axis_iters, sizeof(int) * nprob));
-  c->axis_cap = nprob;
+  GROW(c, d_axis_obj, sizeof(double) * nprob);
+  GROW(c, d_axis_viol, sizeof(double) * 4 * nprob);
+  GROW(c, d_axis_status, sizeof(int) * nprob);
+  GROW(c, d_axis_iters, sizeof(int) * nprob);
   return BTRAPZ_OK;
 }
 
@@ -325,6 +359,13 @@ void btrapz_mqm_table_host(const btrapz_shared *sh, double *table) {
   }
 }
 
+// The M'QM table of the weights (w_s, w_l), built on the device in stream order.
+static void launch_mqm_table(hipStream_t stream, const double *w_s, const double *w_l, double *table) {
+  MqmWeights mw;
+  memcpy(mw.w[0], w_s, sizeof(double) * 4); memcpy(mw.w[1], w_l, sizeof(double) * 4);
+  hipLaunchKernelGGL(mqm_table_kernel, dim3(1), dim3(192), 0, stream, mw, table);
+}
+
 void btrapz_single_forget(btrapz_ctx *c) { if (c) c->single_S = 0; }
 
 // Test hook: the M'QM table as find_traj's single launch receives it (host builder) and as the batched entry points
@@ -335,9 +376,7 @@ BTRAPZ_EXPORT int btrapz_debug_mqm_tables(btrapz_ctx *c, const btrapz_shared *sh
   btrapz_mqm_table_host(sh, host_table);
   double *d = nullptr;
   HIPCHK(c, hipMalloc(&d, sizeof(double) * 168));
-  MqmWeights mw;
-  memcpy(mw.w[0], sh->w_s, sizeof(double) * 4); memcpy(mw.w[1], sh->w_l, sizeof(double) * 4);
-  hipLaunchKernelGGL(mqm_table_kernel, dim3(1), dim3(192), 0, nullptr, mw, d);
+  launch_mqm_table(nullptr, sh->w_s, sh->w_l, d);
   hipError_t e = hipMemcpy(device_table, d, sizeof(double) * 168, hipMemcpyDeviceToHost);
   (void)hipFree(d);
   HIPCHK(c, e);
@@ -347,7 +386,7 @@ BTRAPZ_EXPORT int btrapz_debug_mqm_tables(btrapz_ctx *c, const btrapz_shared *sh
 // Test / analysis hook: iterations and status of the 2 B axis problems of the context's last batched solve
 // ([b][axis], host arrays; synchronises the device).  tools/resume_model.py reads them.
 BTRAPZ_EXPORT int btrapz_debug_axis_records(btrapz_ctx *c, int B, int *iters, int *status) {
-  if (!c || B < 1 || (size_t)2 * B > c->axis_cap || !iters || !status) return BTRAPZ_EINVAL;
+  if (!c || B < 1 || (size_t)2 * B > c->d_axis_iters.cap() || !iters || !status) return BTRAPZ_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   HIPCHK(c, hipMemcpy(iters, c->d_axis_iters, sizeof(int) * 2 * B, hipMemcpyDeviceToHost));
@@ -356,7 +395,7 @@ BTRAPZ_EXPORT int btrapz_debug_axis_records(btrapz_ctx *c, int B, int *iters, in
 }
 // ... and the keys [2][B] the last capped solve's resume launch was bucketed by (0: the axis problem was not handed over)
 BTRAPZ_EXPORT int btrapz_debug_resume_keys(btrapz_ctx *c, int B, int *keys) {
-  if (!c || B < 1 || !keys || c->susp_ints < 400 + 4 * (size_t)B) return BTRAPZ_EINVAL;
+  if (!c || B < 1 || !keys || c->d_susp_ints.cap() < 400 + 4 * (size_t)B) return BTRAPZ_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   HIPCHK(c, hipMemcpy(keys, c->d_susp_ints + 400, sizeof(int) * 2 * B, hipMemcpyDeviceToHost));
@@ -374,40 +413,399 @@ int btrapz_launch_single(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_op
   const double *mqm = in + (size_t)BTRAPZ_NUM_SEG_FIELDS * S + 18;
   a.seg = in; a.init = in + (size_t)BTRAPZ_NUM_SEG_FIELDS * S; a.ref_end = a.init + 6; a.dl_bounds = a.ref_end + 2; a.mqm = mqm;
   // what the kernel reads back stays in device memory: the context's per-axis records and a control-point block
-  int rc = ensure_axis_ws(c, 2);
-  if (rc != BTRAPZ_OK) return rc;
-  if (!c->d_single) HIPCHK(c, hipMalloc(&c->d_single, sizeof(double) * 12 * BTRAPZ_MAX_SEGMENTS));
-  if (c->ws_used && c->ws_stream != stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  TRY(ensure_axis_ws(c, 2));
+  GROW(c, d_single, sizeof(double) * 12 * BTRAPZ_MAX_SEGMENTS);
+  TRY(ws_wait(c, stream));
   a.axis_obj = c->d_axis_obj; a.axis_status = c->d_axis_status; a.axis_iters = c->d_axis_iters;
   a.ctrl = c->d_single; a.queue = nullptr; a.x_out = nullptr; a.axis_viol = nullptr;
   // at most 21 segments: the split form (rows of a segment over three lanes), ~0.8 of the time per iteration
   const bool split_form = S <= 21 && !(opt && opt->split < 0);   // (find_traj maps BTRAPZ_SPLIT onto opt->split)
   if (warm) {
     const size_t nx = 2 * 64 * 3, nl = 2 * 36 * 64, set = nx + nl;
-    if (!c->d_single_warm) HIPCHK(c, hipMalloc(&c->d_single_warm, sizeof(double) * 2 * set));
+    GROW(c, d_single_warm, sizeof(double) * 2 * set);
     double *rd = c->d_single_warm + (size_t)c->single_flip * set, *wr = c->d_single_warm + (size_t)(1 - c->single_flip) * set;
     const bool have = c->single_S == S && c->single_variant == sh->variant;
     // layouts for B = 1, seg_stride = S: x [2][S][3], lam [2][36][1][S]
     a.x0 = have ? rd : nullptr; a.lam0 = have ? rd + nx : nullptr;
     a.x_out = wr; a.lam_out = wr + nx;
     c->single_flip = 1 - c->single_flip; c->single_S = S; c->single_variant = sh->variant;
-    if (split_form)
-      hipLaunchKernelGGL(single_candidate_warm_split_kernel, dim3(1), dim3(128), 0, stream, a, mqm, sh->delta, max_points, out);
-    else
-      hipLaunchKernelGGL(single_candidate_warm_kernel, dim3(1), dim3(128), 0, stream, a, mqm, sh->delta, max_points, out);
-  } else {
-    if (split_form)
-      hipLaunchKernelGGL(single_candidate_split_kernel, dim3(1), dim3(128), 0, stream, a, mqm, sh->delta, max_points, out);
-    else
-      hipLaunchKernelGGL(single_candidate_kernel, dim3(1), dim3(128), 0, stream, a, mqm, sh->delta, max_points, out);
   }
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
+  auto kernel = warm ? (split_form ? single_candidate_warm_split_kernel : single_candidate_warm_kernel)
+                     : (split_form ? single_candidate_split_kernel : single_candidate_kernel);
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(128), 0, stream, a, mqm, sh->delta, max_points, out);
+  TRY(ws_close(c, stream));
+  HIPCHK(c, hipGetLastError());
+  return BTRAPZ_OK;
+}
+
+// ---- the batched solve: what solve_common and btrapz_solve_sets_device share, then solve_common's steps -----------------
+
+// Histogram -> prefix -> scatter: the candidates whose key is listed, bucket by bucket (btrapz_kernels.hip).  ny is the
+// grid's y extent: 2 builds the lists of both axes in one launch each (keys [2][B], tables [2][198], lists [2][B]).
+static void launch_bucket_lists(hipStream_t stream, unsigned ny, int B, int S, const int *keys, int *tables, int *lists,
+                                double *obj, int *status, int *iters, int fixed_S) {
+  const unsigned nb = (unsigned)((B + 255) / 256);
+  hipLaunchKernelGGL(bucket_hist_kernel, dim3(nb, ny), dim3(256), 0, stream, B, S, keys, tables, fixed_S);
+  hipLaunchKernelGGL(bucket_prefix_kernel, dim3(1, ny), dim3(64), 0, stream, tables, fixed_S);
+  hipLaunchKernelGGL(bucket_scatter_kernel, dim3(nb, ny), dim3(256), 0, stream, B, S, keys, tables, lists, obj, status, iters, fixed_S);
+}
+
+// What the choice of form depends on.  split, lean, cap_iter and queue are REQUESTS (0 automatic, > 0 on, < 0 off) that
+// the caller has resolved: solve_common from btrapz_options and, in experiment builds, the environment (solve_requests);
+// btrapz_solve_sets_device from btrapz_options alone, and with cap_iter = -1 (it never runs the two launches).
+struct FormQuery {
+  int B, S, elastic, max_iter, unc_start, resident_waves;
+  bool ragged, warm_kernel, ordered, compact;   // ordered: the launch goes through a candidate list (a.order)
+  int split, lean, cap_iter; bool queue;        // the requests
+  unsigned blocks;                              // wavefronts of the one-launch packed form
+};
+struct Form { bool long_form, split_on, lean_on, capped, queue_on; int cap_iter; };   // cap_iter: iterations of the first of two launches
+
+static Form choose_form(const FormQuery &q) {
+  Form f;
+  f.long_form = !q.ragged && q.S > BTRAPZ_MAX_SEGMENTS;   // one axis problem per workgroup (ipm_solve_long_kernel)
+  f.queue_on = q.queue;
+  // Few candidates: one per wavefront, rows over three lanes (btrapz_options.split; ipm_solve_split_kernel)
+  f.split_on = !q.ordered && !q.warm_kernel && q.S <= 21 &&
+               (q.split > 0 || (q.split == 0 && 2u * (unsigned)q.B <= (unsigned)q.resident_waves));
+  // Two wavefronts per SIMD (btrapz_options.lean / BTRAPZ_LEAN; btrapz_lean.hip): cold solves of at most 64 segments
+  const bool lean_ok = !f.long_form && !f.split_on && !f.queue_on && (q.S >= 3 || q.ragged) && q.S <= BTRAPZ_MAX_SEGMENTS && q.unc_start == 0;   // (uniform batches of one or two segments: the packed form -- only the lean kernels of ragged batches carry the end-lane fix-up)
+  // Automatic: batches that give every SIMD its two wavefronts several times over.  Measured (tools/lean_bench.py,
+  // scenario_1 x 20, packed -> lean, one launch): 512 candidates 0.375 -> 0.435 ms, 2 048 0.447 -> 0.517, 8 192 1.117 ->
+  // 1.032, 16 384 1.964 -> 1.733, 65 536 7.05 -> 5.61: a lone wavefront per SIMD runs the packed form's shorter
+  // instruction stream faster; from about three wavefronts per SIMD on the second resident one pays.
+  const unsigned est_waves = 2u * (unsigned)((size_t)q.B / (size_t)(64 / (q.S < 64 ? q.S : 64)) + 1);
+  // (round 5, re-measured with the final kernels, packed -> lean in one launch, ms: scenario_1 x 20 -- 512 candidates
+  //  0.30 -> 0.34, 2 048 0.40 -> 0.38, 4 096 0.63 -> 0.52, 8 192 0.91 -> 0.78; generic x 10 -- 2 048 0.14 -> 0.17, 4 096
+  //  0.22 -> 0.19, 8 192 0.33 -> 0.29: the crossover sits at about 1.25 wavefronts per SIMD, not at 3)
+  f.lean_on = lean_ok && (q.lean > 0 || (q.lean == 0 && 4u * est_waves >= 5u * (unsigned)q.resident_waves));
+  // Two launches for uniform cold batches much larger than the machine (btrapz_options.cap_iter / BTRAPZ_CAP): every
+  // group stops at cap_iter iterations, the unfinished ones are carried on by a second launch, like with like, the
+  // far-from-converged first (CAPPED / RESUME in btrapz_kernels.hip).  Same iterates, same results.
+  // Measured (tools/cap_bench.py, 65 536 candidates, one launch -> two): scenario_1 x 20 7.00 -> 6.39 ms, its cuboid
+  // variant 6.70 -> 6.35, generic x 20 5.21 -> 5.18, scenario_1 x 10 2.24 -> 2.46 (six groups per wavefront: what a
+  // lone straggler wastes is less than what the second launch costs).  Automatic (cap_iter = 0): 6 for uniform cold
+  // batches of 16 to 64 segments that fill the device at least eight times over; -1: never.
+  // Ragged batches (round 3, late): the same two launches on request (cap_iter > 0), the resume lists bucketed by
+  // segment count instead of by convergence class.  Not automatic: measured on 65 536 candidates, knots -> control
+  // points (tools/pipeline_bench.py, one launch -> cap 8): jittered c_road_s1_3.txt, 8 segments, a quarter of the
+  // candidates infeasible (16-19 iterations against 9-12) 3.20 -> 2.90 ms; scenario_1 at knot level, 18-24 segments
+  // 9.56 -> 9.79; two-car scenes, 7-9 segments, all feasible 3.21 -> 3.54 -- it pays where iteration counts spread
+  // widely, which the library does not know.
+  f.cap_iter = q.cap_iter;
+  // (S <= 32: a wavefront that holds ONE group has nobody to wait for -- with 33..64 segments every group would be
+  //  "alone" at once and a quarter of the batch be written out and read back for nothing: ADVICE r4)
+  if (f.cap_iter == 0 && !q.ragged && q.S >= 16 && q.S <= 32 && q.blocks >= 8u * (unsigned)q.resident_waves) f.cap_iter = 6;
+  f.capped = f.cap_iter > 0 && !f.long_form && !f.split_on && (!q.ordered || q.ragged || q.compact) && !q.warm_kernel && !f.queue_on && q.S <= BTRAPZ_MAX_SEGMENTS &&
+             f.cap_iter < q.max_iter && f.cap_iter + BTRAPZ_CAP_HI < 4000 && q.elastic != 2;   // (4000: the lean record's 12-bit counters)
+  return f;
+}
+
+// Ragged batch with slots for more than 64 segments: the candidates that HAVE more than 64 (the bucket kernels have
+// marked them "no usable corridor") are solved by the long form, one launch per segment count with the candidates of
+// that count listed.  The counts come to the host for this (one synchronisation: horizons beyond 64 s are not the
+// throughput path); cold solves without a rescue pass -- what the long form serves.  The reference has no limit on the
+// segment count (std::vector, src/solve_3d.cc:323-486,729-772).  launch(args, n, s): the long-form kernel of the caller
+// over the n listed candidates of s segments.
+template <class Launch>
+static int solve_long_candidates(btrapz_ctx *c, hipStream_t stream, const KernelArgs &a, const int *seg_count, Launch launch) {
+  const int B = a.B, S = a.S;
+  std::vector<int> counts((size_t)B);
+  HIPCHK(c, hipMemcpyAsync(counts.data(), seg_count, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, stream));
+  HIPCHK(c, hipStreamSynchronize(stream));
+  const int smax = S < BTRAPZ_MAX_SEGMENTS_LONG ? S : BTRAPZ_MAX_SEGMENTS_LONG;
+  std::vector<std::vector<int>> by_count((size_t)smax + 1);
+  size_t n_long = 0;
+  for (int b = 0; b < B; b++)
+    if (counts[b] > BTRAPZ_MAX_SEGMENTS && counts[b] <= smax) { by_count[(size_t)counts[b]].push_back(b); ++n_long; }
+  if (!n_long) return BTRAPZ_OK;
+  GROW(c, d_long_list, sizeof(int) * n_long);
+  std::vector<int> flat; flat.reserve(n_long);
+  for (const auto &l : by_count) flat.insert(flat.end(), l.begin(), l.end());
+  HIPCHK(c, hipMemcpyAsync(c->d_long_list, flat.data(), sizeof(int) * n_long, hipMemcpyHostToDevice, stream));
+  HIPCHK(c, hipStreamSynchronize(stream));   // (flat goes out of scope)
+  size_t off = 0;
+  for (int s = BTRAPZ_MAX_SEGMENTS + 1; s <= smax; s++) {
+    const size_t n = by_count[(size_t)s].size();
+    if (!n) continue;
+    KernelArgs l = a;
+    l.S = s; l.order = c->d_long_list + off; l.bucket_S = (int)n; l.seg_count = nullptr; l.cand_prefix = nullptr; l.wave_prefix = nullptr;
+    launch(l, (unsigned)n, s);
+    HIPCHK(c, hipGetLastError());
+    off += n;
+  }
+  c->last_form |= 16;   // (+ 16: the long form served part of a ragged batch)
+  return BTRAPZ_OK;
+}
+
+// Last step of a solve: per-candidate cost, status and iterations from the per-axis records; closes the launch sequence.
+static int finalize_and_close(btrapz_ctx *c, hipStream_t stream, int B, double *cost, int *status, int *iters) {
+  hipLaunchKernelGGL(finalize_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, c->d_axis_obj, c->d_axis_status,
+                     c->d_axis_iters, cost, status, iters);
+  HIPCHK(c, hipGetLastError());
+  return ws_close(c, stream);
+}
+
+// The kernel arguments of a batched solve that are the same in every form: shapes, the batch, the context's per-axis records.
+static void batch_arguments(btrapz_ctx *c, KernelArgs &a, int B, int S, const double *seg, const double *init, const double *ref_end,
+                            const double *dl_bounds, double *ctrl, const double *mqm) {
+  a.B = B; a.S = S; a.seg_stride = S; a.order = nullptr; a.seg_count = nullptr; a.cand_prefix = nullptr; a.wave_prefix = nullptr;
+  a.seg = seg; a.init = init; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.mqm = mqm;
+  a.ctrl = ctrl; a.axis_obj = c->d_axis_obj; a.axis_status = c->d_axis_status; a.axis_iters = c->d_axis_iters;
+  a.axis_viol = c->d_axis_viol; c->viol_valid = 0;
+  a.x_out = nullptr; a.queue = c->d_queue;
+}
+
+// State of one solve_common call, handed from step to step.
+struct Solve {
+  btrapz_ctx *c; hipStream_t stream; const btrapz_options *opt;
+  int B, S; const int *seg_count;   // S: segments of a uniform batch (seg_count == nullptr), slot stride of a ragged one
+  KernelArgs a;
+  int elastic; bool compact, warm_kernel;
+  unsigned blocks;                  // wavefronts of the one-launch packed / lean form
+};
+
+// Step: the batch-invariant M'QM table, rebuilt only when the weights change.
+static int solve_weights_table(btrapz_ctx *c, const btrapz_shared *sh, hipStream_t stream) {
+  double wkey[8];
+  memcpy(wkey, sh->w_s, sizeof(double) * 4); memcpy(wkey + 4, sh->w_l, sizeof(double) * 4);
+  if (memcmp(wkey, c->h_mqm_w, sizeof(wkey)) == 0) return BTRAPZ_OK;
+  // built on the device, in stream order: no host buffer to keep alive, no synchronisation, and a launch that is
+  // still reading the previous table (same stream, or ordered by the event of ws_open) finishes first
+  launch_mqm_table(stream, sh->w_s, sh->w_l, c->d_mqm);
+  HIPCHK(c, hipGetLastError());
+  memcpy(c->h_mqm_w, wkey, sizeof(wkey));
+  return BTRAPZ_OK;
+}
+
+// Step: pre-pass and ordering.  Sets a.order and the bucket tables where the launches go through a list, and s.blocks.
+static int solve_order_candidates(Solve &s, const btrapz_shared *sh, const int *hint) {
+  btrapz_ctx *c = s.c; KernelArgs &a = s.a;
+  const int B = s.B, S = s.S, *seg_count = s.seg_count;
+  // Candidates that cannot start (btrapz_options.compact): a pre-pass lists the live ones, the launches below take them
+  // through a.order.  Cold solves without a rescue pass only (the rescue pass solves what stalled, axis by axis: it needs
+  // every axis's record); automatic for large ragged batches and large batches of the cuboid variant.
+  const bool warm_args = a.x0 || a.lam0 || a.lam_out;
+  const int compact_opt = s.opt ? s.opt->compact : 0;
+  const unsigned waves_needed = 2u * (unsigned)((size_t)B / (size_t)(64 / (S < 64 ? S : 64)) + 1);
+  s.compact = s.elastic == 0 && !warm_args && !hint && S <= BTRAPZ_MAX_SEGMENTS && a.unc_start == 0 &&
+              (compact_opt > 0 || (compact_opt == 0 && (seg_count || sh->variant == BTRAPZ_CUBOID) && waves_needed >= 3u * (unsigned)c->resident_waves));
+  int *compact_keys = nullptr;
+  if (s.compact) {
+    GROW(c, d_rescue, sizeof(int) * 4 * (size_t)B);   // (keys [B] at the front of the rescue pass's lists: no rescue pass in this solve)
+    compact_keys = c->d_rescue;
+    KernelArgs pa = a;
+    pa.seg_stride = S;
+    const int pre_gpw = 64 / S;   // (S: the slot stride, at most 64 here)
+    hipLaunchKernelGGL(prestart_kernel, dim3((unsigned)((B + pre_gpw - 1) / pre_gpw)), dim3(64), 0, s.stream, pa, seg_count ? 0 : S, seg_count, compact_keys);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (seg_count || hint || s.compact) {
+    GROW(c, d_order, sizeof(int) * (size_t)B);
+    GROW(c, d_meta, sizeof(int) * 198);
+    HIPCHK(c, hipMemsetAsync(c->d_meta, 0, sizeof(int) * 198, s.stream));
+    // keys: segment counts (ragged), hint classes (uniform, fixed_S > 0), or -- compact -- the pre-pass's list keys: the
+    // count / 1 of a live candidate, 0 for one that is not listed (uniform: fixed_S < 0, "a key <= 0 is not listed"); the
+    // pre-pass has written the records of what it dropped, so the scatter kernel writes none
+    const int fixed_S = seg_count ? 0 : (s.compact ? -S : S);
+    const int *keys = s.compact ? compact_keys : seg_count ? seg_count : hint;
+    launch_bucket_lists(s.stream, 1, B, S, keys, c->d_meta, c->d_order, s.compact ? (double *)nullptr : c->d_axis_obj.ptr(),
+                        s.compact ? (int *)nullptr : c->d_axis_status.ptr(), s.compact ? (int *)nullptr : c->d_axis_iters.ptr(), fixed_S);
+    HIPCHK(c, hipGetLastError());
+    a.order = c->d_order; a.seg_count = seg_count; a.cand_prefix = c->d_meta; a.wave_prefix = c->d_meta + 66;
+    a.bucket_S = seg_count ? 0 : S;
+    // upper bound on wavefront pairs without a host round trip: every bucket wastes less than one pair
+    const int gpw_min = seg_count ? 1 : 64 / S;
+    s.blocks = 2u * (unsigned)(B / gpw_min + 65);
+  } else {
+    const int gpw = S <= 64 ? 64 / S : 1;  // axis problems per wavefront; wave w: axis w&1 of candidates (w>>1)*gpw + [0,gpw)
+    s.blocks = 2u * (unsigned)((B + gpw - 1) / gpw);
+  }
+  s.warm_kernel = a.x0 || a.lam0 || a.lam_out;   // (a hint alone only reorders the candidates)
+  return BTRAPZ_OK;
+}
+
+// The requests of btrapz_options for the choice of form, with the environment's word in experiment builds
+// (experiment_env: BTRAPZ_SPLIT is read at every call, the others once).
+static void solve_requests(const btrapz_options *opt, FormQuery &q) {
+  // Uniform cold batches with several candidates per resident wavefront slot may run on persistent wavefronts that
+  // draw candidates from a queue (btrapz_options.queue / BTRAPZ_QUEUE=1): a wavefront's groups then do not wait for
+  // its slowest one, at the price of ~half an iteration per hand-over for all of its groups.  Measured (65 536
+  // candidates, kernel ms off -> on): scenario_1 x 20 6.93 -> 6.59, its cuboid variant (16 % stalling) 6.57 -> 5.71,
+  // generic x 20 5.12 -> 5.33, scenario_1 x 10 2.13 -> 2.34: it pays where iteration counts spread widely, so it is
+  // the caller's choice and off by default.
+#ifdef BTRAPZ_EXPERIMENTS
+  static const int queue_env = [] { const char *q = experiment_env("BTRAPZ_QUEUE"); return q ? (*q == '0' ? -1 : 1) : 0; }();
+  q.queue = queue_env ? queue_env > 0 : (opt && opt->queue > 0);
+#else
+  q.queue = false;   // (btrapz_options.queue: scheduling only, a measured loss -- honoured by experiment builds, ignored here)
+#endif
+  const char *split_q = experiment_env("BTRAPZ_SPLIT");
+  const int split_env = split_q ? (*split_q == '0' ? -1 : 1) : 0;
+  q.split = split_env ? split_env : (opt ? opt->split : 0);
+  static const int cap_env = [] { const char *q = experiment_env("BTRAPZ_CAP"); return q ? atoi(q) : -1; }();
+  q.cap_iter = cap_env > 0 ? cap_env : cap_env == 0 ? -1 : (opt ? opt->cap_iter : 0);   // BTRAPZ_CAP=0: never
+  static const int lean_env = [] { const char *q = experiment_env("BTRAPZ_LEAN"); return q ? (*q == '0' ? -1 : 1) : 0; }();
+  q.lean = lean_env ? lean_env : (opt ? opt->lean : 0);
+}
+
+// Workspace of the two launches: hand-over slots for BTRAPZ_SUSP_PERCENT of the axis problems (a group that finds none simply
+// goes on), 74 doubles per segment each -- 19 KB per slot at 64 segments, 388 MB for 65 536 candidates of 20 -- but
+// never more than BTRAPZ_SUSP_BYTES_MAX.  When the device cannot give it, a solve that chose the two launches by
+// itself (cap_iter = 0) runs as one launch (*slots_out = 0); one that was asked for them (requested) fails with BTRAPZ_ENOMEM.
+static int capped_workspace(Solve &s, bool requested, size_t *slots_out) {
+  btrapz_ctx *c = s.c; const size_t B = (size_t)s.B, S = (size_t)s.S;
+  size_t slots = 2 * B * (size_t)BTRAPZ_SUSP_PERCENT / 100;
+  if (slots < 1024) slots = 1024;
+  const size_t slots_max = (size_t)BTRAPZ_SUSP_BYTES_MAX / (sizeof(double) * 74 * S);
+  if (slots > slots_max) slots = slots_max;
+  if (slots > (size_t)0x7fffffff) slots = (size_t)0x7fffffff;   // (susp_cap is an int)
+  bool ok = slots >= 64;
+  ok = ok && c->d_susp_state.grow(sizeof(double) * slots * 74 * S) == hipSuccess;
+  ok = ok && c->d_susp_ints.grow(sizeof(int) * (400 + 4 * B)) == hipSuccess;   // count[4] tables[2][198] keys[2][B] slots[2B]
+  ok = ok && c->d_rescue.grow(sizeof(int) * 4 * B) == hipSuccess;
+  ok = ok && c->d_rescue_meta.grow(sizeof(int) * 2 * 198) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();   // (the failed allocation's error is handled here)
+    if (requested) { c->err = "btrapz_options.cap_iter: no memory for the hand-over workspace"; return BTRAPZ_ENOMEM; }
+  }
+  *slots_out = ok ? slots : 0;
+  return BTRAPZ_OK;
+}
+
+// The two-launch solve: capped launch, the lists of what it handed over, resume launch.
+static int launch_capped_and_resume(Solve &s, const Form &f, size_t slots) {
+  btrapz_ctx *c = s.c; const int B = s.B, S = s.S;
+  const bool ragged = s.seg_count != nullptr;
+  // (one workspace, one memset: the counter, the bucket tables of both axes and the keys are zeroed together)
+  int *count = c->d_susp_ints, *tables = count + 4, *keys = tables + 2 * 198, *slot_of = keys + 2 * (size_t)B;
+  HIPCHK(c, hipMemsetAsync(count, 0, sizeof(int) * (400 + 2 * (size_t)B), s.stream));
+  KernelArgs p1 = s.a;
+  p1.cap_iter = f.cap_iter; p1.cap_alone = BTRAPZ_CAP_ALONE; p1.cap_hi = f.cap_iter + BTRAPZ_CAP_HI; p1.cap_score = BTRAPZ_CAP_SCORE; p1.susp_cap = (int)slots; p1.susp_state = c->d_susp_state; p1.susp_count = count;
+  p1.susp_slot = slot_of; p1.susp_key = keys;
+  // (the ordered instantiation serves ragged batches and uniform ones that go through a.order -- the pre-pass -- and
+  //  gives a uniform batch the bits of the memory-order one: btrapz_lean_body.h)
+  auto first = f.lean_on ? (p1.order ? ipm_solve_lean_capped_ordered_kernel : ipm_solve_lean_capped_kernel)
+                         : (p1.order ? ipm_solve_capped_ordered_kernel : ipm_solve_capped_kernel);
+  hipLaunchKernelGGL(first, dim3(s.blocks), dim3(64), 0, s.stream, p1, (const double *)c->d_mqm);
+  int *lists = c->d_rescue + 2 * (size_t)B;
+  const int list_S = ragged ? 0 : -S;   // ragged: keys are segment counts; uniform: convergence classes, 0 = not listed
+  // both axes in one launch each (gridDim.y = 2: keys [2][B], tables [2][198], lists [2][B])
+  launch_bucket_lists(s.stream, 2, B, S, keys, tables, lists, nullptr, nullptr, nullptr, list_S);
+  KernelArgs p2 = p1;
+  p2.cap_iter = 0; p2.order = lists; p2.seg_count = nullptr; p2.cand_prefix = tables; p2.wave_prefix = tables + 66;
+  p2.bucket_S = ragged ? 0 : S;
+  // (ragged: no candidate has more than min(S, 64) segments, so no wavefront holds fewer groups than that allows)
+  const unsigned rblocks = 2u * (unsigned)(slots / (size_t)(64 / (S < 64 ? S : 64)) + 65);
+  hipLaunchKernelGGL(f.lean_on ? ipm_solve_lean_resume_kernel : ipm_solve_resume_kernel, dim3(rblocks), dim3(64), 0, s.stream, p2, (const double *)c->d_mqm);
+  c->last_form = f.lean_on ? 11 : 3;
+  return BTRAPZ_OK;
+}
+
+// Step: the main launch -- the form is chosen, the two-launch solve gets its workspace, the kernels go out.
+static int solve_main_launch(Solve &s, Form &f) {
+  btrapz_ctx *c = s.c; KernelArgs &a = s.a;
+  const int B = s.B, S = s.S;
+  FormQuery q{};
+  q.B = B; q.S = S; q.ragged = s.seg_count != nullptr; q.warm_kernel = s.warm_kernel; q.ordered = a.order != nullptr; q.compact = s.compact;
+  q.elastic = s.elastic; q.max_iter = a.max_iter; q.unc_start = a.unc_start; q.resident_waves = c->resident_waves; q.blocks = s.blocks;
+  solve_requests(s.opt, q);
+  f = choose_form(q);
+  if (f.long_form && (a.order || s.warm_kernel || s.elastic == 2 || (s.elastic == 1 && S > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE))) {
+    c->err = "more than 64 segments: uniform cold solve only, rescue pass (elastic = 1) up to 192 segments";
+    return BTRAPZ_EINVAL;
+  }
+  if (s.elastic == 2) return BTRAPZ_OK;   // (elastic rows for every candidate: the rescue pass is the solve)
+  size_t slots = 0;   // (q.cap_iter > 0: asked for by the caller; the automatic choice falls back to one launch without the workspace)
+  if (f.capped) TRY(capped_workspace(s, q.cap_iter > 0, &slots));
+  if (slots) {
+    TRY(launch_capped_and_resume(s, f, slots));
+  } else if (f.long_form) {
+    c->last_form = 2;
+    hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, s.stream, a, (const double *)c->d_mqm);
+  } else if (f.split_on) {
+    c->last_form = 1;
+    hipLaunchKernelGGL(ipm_solve_split_kernel, dim3(2u * (unsigned)B), dim3(64), 0, s.stream, a, (const double *)c->d_mqm);
+#ifdef BTRAPZ_EXPERIMENTS
+  } else if (f.queue_on && !a.order && !s.warm_kernel && s.blocks >= 3u * (unsigned)c->resident_waves) {
+    HIPCHK(c, hipMemsetAsync(c->d_queue, 0, sizeof(int) * 2, s.stream));
+    c->last_form = 4;
+    hipLaunchKernelGGL(ipm_solve_queue_kernel, dim3((unsigned)c->resident_waves & ~1u), dim3(64), 0, s.stream, a, (const double *)c->d_mqm);
+#endif
+  } else if (f.lean_on) {
+    c->last_form = 8;
+    // (a.order: the buckets of a ragged batch, or the hint classes / the pre-pass's list of a uniform one)
+    auto lean_kernel = s.warm_kernel ? (a.order ? ipm_solve_lean_warm_ordered_kernel : ipm_solve_lean_warm_kernel)
+                                     : (a.order ? ipm_solve_lean_ordered_kernel : ipm_solve_lean_kernel);
+    hipLaunchKernelGGL(lean_kernel, dim3(s.blocks), dim3(64), 0, s.stream, a, (const double *)c->d_mqm);
+  } else {
+    c->last_form = 0;
+    auto kernel = s.warm_kernel ? (a.order ? ipm_solve_warm_ordered_kernel : ipm_solve_warm_kernel)
+                                : (a.order ? ipm_solve_ordered_kernel : ipm_solve_kernel);
+    hipLaunchKernelGGL(kernel, dim3(s.blocks), dim3(64), 0, s.stream, a, (const double *)c->d_mqm);
+  }
+  HIPCHK(c, hipGetLastError());
+  return BTRAPZ_OK;
+}
+
+// The arguments of both rescue passes: cold, and patient.
+// Least-violation problems take 25-40 iterations, and up to 60 where a row's violation is fixed by the data (an
+// initial state outside segment 0's rows): its multiplier has to grow to violation / delta before the score moves.
+// The pass is rare and not on the throughput path: be patient (the oracle's relaxed solve is; with these limits every
+// one of 6 000 fuzzed find_traj calls decides as it does, with 80 / 2x / 2x six of 4 800 did not).
+static KernelArgs rescue_arguments(const KernelArgs &a) {
+  KernelArgs e = a;
+  e.x0 = nullptr; e.lam0 = nullptr; e.lam_out = nullptr;
+  e.max_iter = a.max_iter < 120 ? 120 : a.max_iter;
+  e.tau_iters = 0;                                  // conservative step rule throughout
+  e.stall_start = 4 * BTRAPZ_STALL_START; e.stall_len = 4 * BTRAPZ_STALL_LENGTH;
+  return e;
+}
+
+// Step: the rescue pass (btrapz_options.elastic) of the long form and of the packed form.
+static int solve_rescue_pass(Solve &s, bool long_form) {
+  btrapz_ctx *c = s.c; const int B = s.B, S = s.S;
+  if (long_form) {
+    // Rescue pass of the long form: one workgroup per axis problem again; those whose problem did not stall leave at once
+    HIPCHK(c, hipMemsetAsync(c->d_axis_viol, 0, sizeof(double) * 8 * (size_t)B, s.stream));
+    c->viol_valid = (size_t)B;
+    KernelArgs e = rescue_arguments(s.a);
+    e.order = nullptr;
+    hipLaunchKernelGGL(ipm_solve_long_elastic_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, s.stream, e, (const double *)c->d_mqm);
+    HIPCHK(c, hipGetLastError());
+    return BTRAPZ_OK;
+  }
+  // Rescue pass: the axis problems that stalled (elastic == 2: all of them) are listed per axis, bucketed by
+  // segment count with the machinery of the ragged batches, and solved again with elastic rows.  The lists are
+  // built on the device; the launch is sized for the worst case and its unused wavefronts leave at once.
+  GROW(c, d_rescue, sizeof(int) * 4 * (size_t)B);
+  GROW(c, d_rescue_meta, sizeof(int) * 2 * 198);
+  HIPCHK(c, hipMemsetAsync(c->d_axis_viol, 0, sizeof(double) * 8 * (size_t)B, s.stream));
+  c->viol_valid = (size_t)B;
+  int *keys = c->d_rescue, *lists = c->d_rescue + 2 * (size_t)B;
+  const unsigned nb = (unsigned)((B + 255) / 256);
+  if (s.elastic == 2)
+    hipLaunchKernelGGL(rescue_init_kernel, dim3(nb), dim3(256), 0, s.stream, B, S, s.seg_count, c->d_axis_obj,
+                       c->d_axis_status, c->d_axis_iters);
+  hipLaunchKernelGGL(rescue_keys_kernel, dim3(nb), dim3(256), 0, s.stream, B, S, s.seg_count, (const int *)c->d_axis_status,
+                     keys, s.elastic == 2 ? 1 : 0);
+  HIPCHK(c, hipMemsetAsync(c->d_rescue_meta, 0, sizeof(int) * 2 * 198, s.stream));
+  for (int ax = 0; ax < 2; ax++)   // (an axis at a time: three launches each)
+    launch_bucket_lists(s.stream, 1, B, S, keys + (size_t)ax * B, c->d_rescue_meta + ax * 198, lists + (size_t)ax * B, nullptr, nullptr, nullptr, 0);
+  HIPCHK(c, hipGetLastError());
+  KernelArgs e = rescue_arguments(s.a);
+  e.order = lists; e.seg_count = s.seg_count; e.cand_prefix = c->d_rescue_meta; e.wave_prefix = c->d_rescue_meta + 66;
+  e.bucket_S = 0;
+  const int smax = s.seg_count ? (S < 64 ? S : 64) : S;
+  const unsigned eblocks = 2u * (unsigned)(B / (64 / smax) + 65);
+  hipLaunchKernelGGL(ipm_solve_elastic_kernel, dim3(eblocks), dim3(64), 0, s.stream, e, (const double *)c->d_mqm);
   HIPCHK(c, hipGetLastError());
   return BTRAPZ_OK;
 }
 
 // Uniform batches: seg_count == nullptr, S segments each.  Ragged: S is the slot stride, seg_count[b] the use.
+// The steps: validate -> open the launch sequence, per-axis records -> M'QM table -> kernel arguments and options ->
+// pre-pass and ordering -> main launch -> rescue pass -> long candidates of a ragged batch -> finalise and close.
 static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_options *opt, const btrapz_warm *warm,
                         int B, int S, const int *seg_count, const double *seg, const double *init, const double *ref_end,
                         const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters, void *stream_) {
@@ -418,32 +816,15 @@ static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_opt
     return BTRAPZ_EINVAL;
   }
   if (!options_ok(c, opt)) return BTRAPZ_EINVAL;
-  hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
-  int rc = ensure_axis_ws(c, 2 * (size_t)B);
-  if (rc != BTRAPZ_OK) return rc;
-  // batch-invariant M'QM table: rebuilt only when the weights change
-  double wkey[8];
-  memcpy(wkey, sh->w_s, sizeof(double) * 4); memcpy(wkey + 4, sh->w_l, sizeof(double) * 4);
-  if (memcmp(wkey, c->h_mqm_w, sizeof(wkey)) != 0) {
-    // built on the device, in stream order: no host buffer to keep alive, no synchronisation, and a launch that is
-    // still reading the previous table (same stream, or ordered by the event above) finishes first
-    MqmWeights mw;
-    memcpy(mw.w[0], sh->w_s, sizeof(double) * 4); memcpy(mw.w[1], sh->w_l, sizeof(double) * 4);
-    hipLaunchKernelGGL(mqm_table_kernel, dim3(1), dim3(192), 0, stream, mw, c->d_mqm);
-    HIPCHK(c, hipGetLastError());
-    memcpy(c->h_mqm_w, wkey, sizeof(wkey));
-  }
-  KernelArgs a;
-  fill_parameters(a, sh, opt, warm);
-  a.B = B; a.S = S; a.seg_stride = S; a.order = nullptr; a.seg_count = nullptr; a.cand_prefix = nullptr; a.wave_prefix = nullptr;
-  a.seg = seg; a.init = init; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.mqm = c->d_mqm;
-  a.ctrl = ctrl; a.axis_obj = c->d_axis_obj; a.axis_status = c->d_axis_status; a.axis_iters = c->d_axis_iters;
-  a.axis_viol = c->d_axis_viol; c->viol_valid = 0;
-  a.x_out = nullptr;
-  const int elastic = opt ? opt->elastic : 0;
-  if (elastic < 0 || elastic > 2) { c->err = "invalid argument: btrapz_options.elastic"; return BTRAPZ_EINVAL; }
+  Solve s;
+  s.c = c; s.stream = (hipStream_t)stream_; s.opt = opt; s.B = B; s.S = S; s.seg_count = seg_count;
+  TRY(ws_open(c, s.stream));
+  TRY(ensure_axis_ws(c, 2 * (size_t)B));
+  TRY(solve_weights_table(c, sh, s.stream));
+  KernelArgs &a = s.a; fill_parameters(a, sh, opt, warm);
+  batch_arguments(c, a, B, S, seg, init, ref_end, dl_bounds, ctrl, c->d_mqm);
+  s.elastic = opt ? opt->elastic : 0;
+  if (s.elastic < 0 || s.elastic > 2) { c->err = "invalid argument: btrapz_options.elastic"; return BTRAPZ_EINVAL; }
 #ifndef BTRAPZ_EXPERIMENTS
   // the two experimental schedules exist in -DBTRAPZ_EXPERIMENTS builds only: asking this build for one is an error, not a
   // silent default (btrapz_build_has_experiments() tells a caller which build it holds)
@@ -452,317 +833,17 @@ static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_opt
     return BTRAPZ_EINVAL;
   }
 #endif
-  unsigned blocks;
-  const int *hint = (warm && !seg_count) ? warm->hint : nullptr;   // uniform batches only
-  // Candidates that cannot start (btrapz_options.compact): a pre-pass lists the live ones, the launches below take them
-  // through a.order.  Cold solves without a rescue pass only (the rescue pass solves what stalled, axis by axis: it needs
-  // every axis's record); automatic for large ragged batches and large batches of the cuboid variant.
-  const bool warm_args = a.x0 || a.lam0 || a.lam_out;
-  const int compact_opt = opt ? opt->compact : 0;
-  const unsigned waves_needed = 2u * (unsigned)((size_t)B / (size_t)(64 / (S < 64 ? S : 64)) + 1);
-  const bool compact = elastic == 0 && !warm_args && !hint && S <= BTRAPZ_MAX_SEGMENTS && a.unc_start == 0 &&
-                       (compact_opt > 0 || (compact_opt == 0 && (seg_count || sh->variant == BTRAPZ_CUBOID) && waves_needed >= 3u * (unsigned)c->resident_waves));
-  int *compact_keys = nullptr;
-  if (compact) {
-    if (2 * (size_t)B > c->rescue_cap) {   // (keys [B] at the front of the rescue pass's lists: no rescue pass in this solve)
-      (void)hipFree(c->d_rescue); c->d_rescue = nullptr; c->rescue_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_rescue, sizeof(int) * 4 * (size_t)B));
-      c->rescue_cap = 2 * (size_t)B;
-    }
-    compact_keys = c->d_rescue;
-    KernelArgs pa = a;
-    pa.seg_stride = S;
-    const int pre_gpw = 64 / S;   // (S: the slot stride, at most 64 here)
-    hipLaunchKernelGGL(prestart_kernel, dim3((unsigned)((B + pre_gpw - 1) / pre_gpw)), dim3(64), 0, stream, pa, seg_count ? 0 : S, seg_count, compact_keys);
-    HIPCHK(c, hipGetLastError());
+  TRY(solve_order_candidates(s, sh, (warm && !seg_count) ? warm->hint : nullptr));   // (a hint: uniform batches only)
+  Form f;
+  TRY(solve_main_launch(s, f));
+  if (s.elastic) TRY(solve_rescue_pass(s, f.long_form));
+  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && !s.warm_kernel && s.elastic == 0) {
+    auto launch = [&](const KernelArgs &l, unsigned n, int segs) {
+      hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, s.stream, l, (const double *)c->d_mqm);
+    };
+    TRY(solve_long_candidates(c, s.stream, a, seg_count, launch));
   }
-  if (seg_count || hint || compact) {
-    if ((size_t)B > c->order_cap) {
-      (void)hipFree(c->d_order); c->d_order = nullptr; c->order_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_order, sizeof(int) * (size_t)B));
-      c->order_cap = B;
-    }
-    if (!c->d_meta) HIPCHK(c, hipMalloc(&c->d_meta, sizeof(int) * 198));
-    HIPCHK(c, hipMemsetAsync(c->d_meta, 0, sizeof(int) * 198, stream));
-    const unsigned nb = (unsigned)((B + 255) / 256);
-    // keys: segment counts (ragged), hint classes (uniform, fixed_S > 0), or -- compact -- the pre-pass's list keys: the
-    // count / 1 of a live candidate, 0 for one that is not listed (uniform: fixed_S < 0, "a key <= 0 is not listed"); the
-    // pre-pass has written the records of what it dropped, so the scatter kernel writes none
-    const int fixed_S = seg_count ? 0 : (compact ? -S : S);
-    const int *keys = compact ? compact_keys : seg_count ? seg_count : hint;
-    hipLaunchKernelGGL(bucket_hist_kernel, dim3(nb), dim3(256), 0, stream, B, S, keys, c->d_meta, fixed_S);
-    hipLaunchKernelGGL(bucket_prefix_kernel, dim3(1), dim3(64), 0, stream, c->d_meta, fixed_S);
-    hipLaunchKernelGGL(bucket_scatter_kernel, dim3(nb), dim3(256), 0, stream, B, S, keys, c->d_meta, c->d_order,
-                       compact ? (double *)nullptr : c->d_axis_obj, compact ? (int *)nullptr : c->d_axis_status,
-                       compact ? (int *)nullptr : c->d_axis_iters, fixed_S);
-    HIPCHK(c, hipGetLastError());
-    a.order = c->d_order; a.seg_count = seg_count; a.cand_prefix = c->d_meta; a.wave_prefix = c->d_meta + 66;
-    a.bucket_S = seg_count ? 0 : S;
-    // upper bound on wavefront pairs without a host round trip: every bucket wastes less than one pair
-    const int gpw_min = seg_count ? 1 : 64 / S;
-    blocks = 2u * (unsigned)(B / gpw_min + 65);
-  } else {
-    const int gpw = S <= 64 ? 64 / S : 1;  // axis problems per wavefront; wave w: axis w&1 of candidates (w>>1)*gpw + [0,gpw)
-    blocks = 2u * (unsigned)((B + gpw - 1) / gpw);
-  }
-  const bool warm_kernel = a.x0 || a.lam0 || a.lam_out;   // (a hint alone only reorders the candidates)
-  const bool long_form = !seg_count && S > BTRAPZ_MAX_SEGMENTS;   // one axis problem per workgroup (ipm_solve_long_kernel)
-  if (long_form && (a.order || warm_kernel || elastic == 2 || (elastic == 1 && S > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE))) {
-    c->err = "more than 64 segments: uniform cold solve only, rescue pass (elastic = 1) up to 192 segments";
-    return BTRAPZ_EINVAL;
-  }
-  auto kernel = warm_kernel ? (a.order ? ipm_solve_warm_ordered_kernel : ipm_solve_warm_kernel)
-                            : (a.order ? ipm_solve_ordered_kernel : ipm_solve_kernel);
-  if (elastic != 2) {
-    // Uniform cold batches with several candidates per resident wavefront slot may run on persistent wavefronts that
-    // draw candidates from a queue (btrapz_options.queue / BTRAPZ_QUEUE=1): a wavefront's groups then do not wait for
-    // its slowest one, at the price of ~half an iteration per hand-over for all of its groups.  Measured (65 536
-    // candidates, kernel ms off -> on): scenario_1 x 20 6.93 -> 6.59, its cuboid variant (16 % stalling) 6.57 -> 5.71,
-    // generic x 20 5.12 -> 5.33, scenario_1 x 10 2.13 -> 2.34: it pays where iteration counts spread widely, so it is
-    // the caller's choice and off by default.
-#ifdef BTRAPZ_EXPERIMENTS
-    static const int queue_env = [] { const char *q = experiment_env("BTRAPZ_QUEUE"); return q ? (*q == '0' ? -1 : 1) : 0; }();
-    const bool queue_on = queue_env ? queue_env > 0 : (opt && opt->queue > 0);
-#else
-    const bool queue_on = false;   // (btrapz_options.queue: scheduling only, a measured loss -- honoured by experiment builds, ignored here)
-#endif
-    a.queue = c->d_queue;
-    // Few candidates: one per wavefront, rows over three lanes (btrapz_options.split; ipm_solve_split_kernel)
-    const char *split_q = experiment_env("BTRAPZ_SPLIT");
-    const int split_env = split_q ? (*split_q == '0' ? -1 : 1) : 0;
-    const int split_opt = split_env ? split_env : (opt ? opt->split : 0);
-    const bool split_on = !a.order && !warm_kernel && S <= 21 &&
-                          (split_opt > 0 || (split_opt == 0 && 2u * (unsigned)B <= (unsigned)c->resident_waves));
-    // Two launches for uniform cold batches much larger than the machine (btrapz_options.cap_iter / BTRAPZ_CAP): every
-    // group stops at cap_iter iterations, the unfinished ones are carried on by a second launch, like with like, the
-    // far-from-converged first (CAPPED / RESUME in btrapz_kernels.hip).  Same iterates, same results.
-    static const int cap_env = [] { const char *q = experiment_env("BTRAPZ_CAP"); return q ? atoi(q) : -1; }();
-    // Measured (tools/cap_bench.py, 65 536 candidates, one launch -> two): scenario_1 x 20 7.00 -> 6.39 ms, its cuboid
-    // variant 6.70 -> 6.35, generic x 20 5.21 -> 5.18, scenario_1 x 10 2.24 -> 2.46 (six groups per wavefront: what a
-    // lone straggler wastes is less than what the second launch costs).  Automatic (cap_iter = 0): 6 for uniform cold
-    // batches of 16 to 64 segments that fill the device at least eight times over; -1: never.
-    // Ragged batches (round 3, late): the same two launches on request (cap_iter > 0), the resume lists bucketed by
-    // segment count instead of by convergence class.  Not automatic: measured on 65 536 candidates, knots -> control
-    // points (tools/pipeline_bench.py, one launch -> cap 8): jittered c_road_s1_3.txt, 8 segments, a quarter of the
-    // candidates infeasible (16-19 iterations against 9-12) 3.20 -> 2.90 ms; scenario_1 at knot level, 18-24 segments
-    // 9.56 -> 9.79; two-car scenes, 7-9 segments, all feasible 3.21 -> 3.54 -- it pays where iteration counts spread
-    // widely, which the library does not know.
-    int cap_iter = cap_env > 0 ? cap_env : cap_env == 0 ? -1 : (opt ? opt->cap_iter : 0);   // BTRAPZ_CAP=0: never
-    // Two wavefronts per SIMD (btrapz_options.lean / BTRAPZ_LEAN; btrapz_lean.hip): cold solves of at most 64 segments
-    static const int lean_env = [] { const char *q = experiment_env("BTRAPZ_LEAN"); return q ? (*q == '0' ? -1 : 1) : 0; }();
-    const int lean_opt = lean_env ? lean_env : (opt ? opt->lean : 0);
-    const bool lean_ok = !long_form && !split_on && !queue_on && (S >= 3 || seg_count) && S <= BTRAPZ_MAX_SEGMENTS && a.unc_start == 0;   // (uniform batches of one or two segments: the packed form -- only the lean kernels of ragged batches carry the end-lane fix-up)
-    // Automatic: batches that give every SIMD its two wavefronts several times over.  Measured (tools/lean_bench.py,
-    // scenario_1 x 20, packed -> lean, one launch): 512 candidates 0.375 -> 0.435 ms, 2 048 0.447 -> 0.517, 8 192 1.117 ->
-    // 1.032, 16 384 1.964 -> 1.733, 65 536 7.05 -> 5.61: a lone wavefront per SIMD runs the packed form's shorter
-    // instruction stream faster; from about three wavefronts per SIMD on the second resident one pays.
-    const unsigned est_waves = 2u * (unsigned)((size_t)B / (size_t)(64 / (S < 64 ? S : 64)) + 1);
-    // (round 5, re-measured with the final kernels, packed -> lean in one launch, ms: scenario_1 x 20 -- 512 candidates
-    //  0.30 -> 0.34, 2 048 0.40 -> 0.38, 4 096 0.63 -> 0.52, 8 192 0.91 -> 0.78; generic x 10 -- 2 048 0.14 -> 0.17, 4 096
-    //  0.22 -> 0.19, 8 192 0.33 -> 0.29: the crossover sits at about 1.25 wavefronts per SIMD, not at 3)
-    const bool lean_on = lean_ok && (lean_opt > 0 || (lean_opt == 0 && 4u * est_waves >= 5u * (unsigned)c->resident_waves));
-    const bool ragged = seg_count != nullptr;
-    const bool cap_requested = cap_iter > 0;   // (by the caller; the automatic choice below falls back to one launch when the workspace cannot be had)
-    // (S <= 32: a wavefront that holds ONE group has nobody to wait for -- with 33..64 segments every group would be
-    //  "alone" at once and a quarter of the batch be written out and read back for nothing: ADVICE r4)
-    if (cap_iter == 0 && !ragged && S >= 16 && S <= 32 && blocks >= 8u * (unsigned)c->resident_waves) cap_iter = 6;
-    const bool capped = cap_iter > 0 && !long_form && !split_on && (!a.order || ragged || compact) && !warm_kernel && !queue_on && S <= BTRAPZ_MAX_SEGMENTS &&
-                        cap_iter < a.max_iter && cap_iter + BTRAPZ_CAP_HI < 4000 && elastic != 2;   // (4000: the lean record's 12-bit counters)
-    // Workspace of the two launches: hand-over slots for BTRAPZ_SUSP_PERCENT of the axis problems (a group that finds none simply
-    // goes on), 74 doubles per segment each -- 19 KB per slot at 64 segments, 388 MB for 65 536 candidates of 20 -- but
-    // never more than BTRAPZ_SUSP_BYTES_MAX.  When the device cannot give it, a solve that chose the two launches by
-    // itself (cap_iter = 0) runs as one launch; one that was asked for them (cap_iter > 0) fails with BTRAPZ_ENOMEM.
-    size_t slots = 0;
-    bool capped_ws = false;
-    if (capped) {
-      slots = 2 * (size_t)B * (size_t)BTRAPZ_SUSP_PERCENT / 100;
-      if (slots < 1024) slots = 1024;
-      const size_t slots_max = (size_t)BTRAPZ_SUSP_BYTES_MAX / (sizeof(double) * 74 * (size_t)S);
-      if (slots > slots_max) slots = slots_max;
-      if (slots > (size_t)0x7fffffff) slots = (size_t)0x7fffffff;   // (susp_cap is an int)
-      const size_t need_state = slots * 74 * (size_t)S, need_ints = 400 + 4 * (size_t)B;   // count[4] tables[2][198] keys[2][B] slots[2B]
-      bool ok = slots >= 64;
-      if (ok && need_state > c->susp_state_doubles) {
-        (void)hipFree(c->d_susp_state); c->d_susp_state = nullptr; c->susp_state_doubles = 0;
-        if (hipMalloc(&c->d_susp_state, sizeof(double) * need_state) == hipSuccess) c->susp_state_doubles = need_state;
-        else { c->d_susp_state = nullptr; ok = false; }
-      }
-      if (ok && need_ints > c->susp_ints) {
-        (void)hipFree(c->d_susp_ints); c->d_susp_ints = nullptr; c->susp_ints = 0;
-        if (hipMalloc(&c->d_susp_ints, sizeof(int) * need_ints) == hipSuccess) c->susp_ints = need_ints;
-        else { c->d_susp_ints = nullptr; ok = false; }
-      }
-      if (ok && 2 * (size_t)B > c->rescue_cap) {
-        (void)hipFree(c->d_rescue); c->d_rescue = nullptr; c->rescue_cap = 0;
-        if (hipMalloc(&c->d_rescue, sizeof(int) * 4 * (size_t)B) == hipSuccess) c->rescue_cap = 2 * (size_t)B;
-        else { c->d_rescue = nullptr; ok = false; }
-      }
-      if (ok && !c->d_rescue_meta && hipMalloc(&c->d_rescue_meta, sizeof(int) * 2 * 198) != hipSuccess) { c->d_rescue_meta = nullptr; ok = false; }
-      if (!ok) {
-        (void)hipGetLastError();   // (the failed allocation's error is handled here)
-        if (cap_requested) { c->err = "btrapz_options.cap_iter: no memory for the hand-over workspace"; return BTRAPZ_ENOMEM; }
-      }
-      capped_ws = ok;
-    }
-    if (capped && capped_ws) {
-      // (one workspace, one memset: the counter, the bucket tables of both axes and the keys are zeroed together)
-      int *count = c->d_susp_ints, *tables = count + 4, *keys = tables + 2 * 198, *slot_of = keys + 2 * (size_t)B;
-      HIPCHK(c, hipMemsetAsync(count, 0, sizeof(int) * (400 + 2 * (size_t)B), stream));
-      KernelArgs p1 = a;
-      p1.cap_iter = cap_iter; p1.cap_alone = BTRAPZ_CAP_ALONE; p1.cap_hi = cap_iter + BTRAPZ_CAP_HI; p1.cap_score = BTRAPZ_CAP_SCORE; p1.susp_cap = (int)slots; p1.susp_state = c->d_susp_state; p1.susp_count = count;
-      p1.susp_slot = slot_of; p1.susp_key = keys;
-      // (the ordered instantiation serves ragged batches and uniform ones that go through a.order -- the pre-pass -- and
-      //  gives a uniform batch the bits of the memory-order one: btrapz_lean_body.h)
-      if (lean_on) {
-        if (p1.order) hipLaunchKernelGGL(ipm_solve_lean_capped_ordered_kernel, dim3(blocks), dim3(64), 0, stream, p1, (const double *)c->d_mqm);
-        else hipLaunchKernelGGL(ipm_solve_lean_capped_kernel, dim3(blocks), dim3(64), 0, stream, p1, (const double *)c->d_mqm);
-      } else {
-        if (p1.order) hipLaunchKernelGGL(ipm_solve_capped_ordered_kernel, dim3(blocks), dim3(64), 0, stream, p1, (const double *)c->d_mqm);
-        else hipLaunchKernelGGL(ipm_solve_capped_kernel, dim3(blocks), dim3(64), 0, stream, p1, (const double *)c->d_mqm);
-      }
-      int *lists = c->d_rescue + 2 * (size_t)B;
-      const unsigned nb = (unsigned)((B + 255) / 256);
-      const int list_S = ragged ? 0 : -S;   // ragged: keys are segment counts; uniform: convergence classes, 0 = not listed
-      // both axes in one launch each (gridDim.y = 2: keys [2][B], tables [2][198], lists [2][B])
-      hipLaunchKernelGGL(bucket_hist_kernel, dim3(nb, 2), dim3(256), 0, stream, B, S, (const int *)keys, tables, list_S);
-      hipLaunchKernelGGL(bucket_prefix_kernel, dim3(1, 2), dim3(64), 0, stream, tables, list_S);
-      hipLaunchKernelGGL(bucket_scatter_kernel, dim3(nb, 2), dim3(256), 0, stream, B, S, (const int *)keys, tables, lists,
-                         (double *)nullptr, (int *)nullptr, (int *)nullptr, list_S);
-      KernelArgs p2 = p1;
-      p2.cap_iter = 0; p2.order = lists; p2.seg_count = nullptr; p2.cand_prefix = tables; p2.wave_prefix = tables + 66;
-      p2.bucket_S = ragged ? 0 : S;
-      // (ragged: no candidate has more than min(S, 64) segments, so no wavefront holds fewer groups than that allows)
-      const unsigned rblocks = 2u * (unsigned)(slots / (size_t)(64 / (S < 64 ? S : 64)) + 65);
-      if (lean_on) hipLaunchKernelGGL(ipm_solve_lean_resume_kernel, dim3(rblocks), dim3(64), 0, stream, p2, (const double *)c->d_mqm);
-      else hipLaunchKernelGGL(ipm_solve_resume_kernel, dim3(rblocks), dim3(64), 0, stream, p2, (const double *)c->d_mqm);
-      c->last_form = lean_on ? 11 : 3;
-    } else if (long_form) {
-      c->last_form = 2;
-      hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, stream, a,
-                         (const double *)c->d_mqm);
-    } else if (split_on) {
-      c->last_form = 1;
-      hipLaunchKernelGGL(ipm_solve_split_kernel, dim3(2u * (unsigned)B), dim3(64), 0, stream, a, (const double *)c->d_mqm);
-#ifdef BTRAPZ_EXPERIMENTS
-    } else if (queue_on && !a.order && !warm_kernel && blocks >= 3u * (unsigned)c->resident_waves) {
-      HIPCHK(c, hipMemsetAsync(c->d_queue, 0, sizeof(int) * 2, stream));
-      c->last_form = 4;
-      hipLaunchKernelGGL(ipm_solve_queue_kernel, dim3((unsigned)c->resident_waves & ~1u), dim3(64), 0, stream, a,
-                         (const double *)c->d_mqm);
-#endif
-    } else if (lean_on) {
-      c->last_form = 8;
-      // (a.order: the buckets of a ragged batch, or the hint classes / the pre-pass's list of a uniform one)
-      auto lean_kernel = warm_kernel ? (a.order ? ipm_solve_lean_warm_ordered_kernel : ipm_solve_lean_warm_kernel)
-                                     : (a.order ? ipm_solve_lean_ordered_kernel : ipm_solve_lean_kernel);
-      hipLaunchKernelGGL(lean_kernel, dim3(blocks), dim3(64), 0, stream, a, (const double *)c->d_mqm);
-    } else {
-      c->last_form = 0;
-      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, a, (const double *)c->d_mqm);
-    }
-    HIPCHK(c, hipGetLastError());
-  }
-  if (elastic && long_form) {
-    // Rescue pass of the long form: one workgroup per axis problem again; those whose problem did not stall leave at once
-    HIPCHK(c, hipMemsetAsync(c->d_axis_viol, 0, sizeof(double) * 8 * (size_t)B, stream));
-    c->viol_valid = (size_t)B;
-    KernelArgs e = a;
-    e.order = nullptr; e.x0 = nullptr; e.lam0 = nullptr; e.lam_out = nullptr;
-    e.max_iter = a.max_iter < 120 ? 120 : a.max_iter;   // (as below)
-    e.tau_iters = 0;
-    e.stall_start = 4 * BTRAPZ_STALL_START; e.stall_len = 4 * BTRAPZ_STALL_LENGTH;
-    hipLaunchKernelGGL(ipm_solve_long_elastic_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, stream, e,
-                       (const double *)c->d_mqm);
-    HIPCHK(c, hipGetLastError());
-  } else if (elastic) {
-    // Rescue pass: the axis problems that stalled (elastic == 2: all of them) are listed per axis, bucketed by
-    // segment count with the machinery of the ragged batches, and solved again with elastic rows.  The lists are
-    // built on the device; the launch is sized for the worst case and its unused wavefronts leave at once.
-    if (2 * (size_t)B > c->rescue_cap) {
-      (void)hipFree(c->d_rescue); c->d_rescue = nullptr; c->rescue_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_rescue, sizeof(int) * 4 * (size_t)B));
-      c->rescue_cap = 2 * (size_t)B;
-    }
-    if (!c->d_rescue_meta) HIPCHK(c, hipMalloc(&c->d_rescue_meta, sizeof(int) * 2 * 198));
-    HIPCHK(c, hipMemsetAsync(c->d_axis_viol, 0, sizeof(double) * 8 * (size_t)B, stream));
-    c->viol_valid = (size_t)B;
-    int *keys = c->d_rescue, *lists = c->d_rescue + 2 * (size_t)B;
-    const unsigned nb = (unsigned)((B + 255) / 256);
-    if (elastic == 2)
-      hipLaunchKernelGGL(rescue_init_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, c->d_axis_obj,
-                         c->d_axis_status, c->d_axis_iters);
-    hipLaunchKernelGGL(rescue_keys_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, (const int *)c->d_axis_status,
-                       keys, elastic == 2 ? 1 : 0);
-    HIPCHK(c, hipMemsetAsync(c->d_rescue_meta, 0, sizeof(int) * 2 * 198, stream));
-    for (int ax = 0; ax < 2; ax++) {
-      int *meta = c->d_rescue_meta + ax * 198;
-      const int *k = keys + (size_t)ax * B;
-      hipLaunchKernelGGL(bucket_hist_kernel, dim3(nb), dim3(256), 0, stream, B, S, k, meta, 0);
-      hipLaunchKernelGGL(bucket_prefix_kernel, dim3(1), dim3(64), 0, stream, meta, 0);
-      hipLaunchKernelGGL(bucket_scatter_kernel, dim3(nb), dim3(256), 0, stream, B, S, k, meta, lists + (size_t)ax * B,
-                         (double *)nullptr, (int *)nullptr, (int *)nullptr, 0);
-    }
-    HIPCHK(c, hipGetLastError());
-    KernelArgs e = a;
-    e.order = lists; e.seg_count = seg_count; e.cand_prefix = c->d_rescue_meta; e.wave_prefix = c->d_rescue_meta + 66;
-    e.bucket_S = 0; e.x0 = nullptr; e.lam0 = nullptr; e.lam_out = nullptr;
-    // Least-violation problems take 25-40 iterations, and up to 60 where a row's violation is fixed by the data (an
-    // initial state outside segment 0's rows): its multiplier has to grow to violation / delta before the score moves.
-    // The pass is rare and not on the throughput path: be patient (the oracle's relaxed solve is; with these limits every
-    // one of 6 000 fuzzed find_traj calls decides as it does, with 80 / 2x / 2x six of 4 800 did not).
-    e.max_iter = a.max_iter < 120 ? 120 : a.max_iter;
-    e.tau_iters = 0;                                  // conservative step rule throughout
-    e.stall_start = 4 * BTRAPZ_STALL_START; e.stall_len = 4 * BTRAPZ_STALL_LENGTH;
-    const int smax = seg_count ? (S < 64 ? S : 64) : S;
-    const unsigned eblocks = 2u * (unsigned)(B / (64 / smax) + 65);
-    hipLaunchKernelGGL(ipm_solve_elastic_kernel, dim3(eblocks), dim3(64), 0, stream, e, (const double *)c->d_mqm);
-    HIPCHK(c, hipGetLastError());
-  }
-  // Ragged batch with slots for more than 64 segments: the candidates that HAVE more than 64 (the bucket kernels have
-  // marked them "no usable corridor") are solved by the long form, one launch per segment count with the candidates of
-  // that count listed.  The counts come to the host for this (one synchronisation: horizons beyond 64 s are not the
-  // throughput path); cold solves without a rescue pass -- what the long form serves.  The reference has no limit on the
-  // segment count (std::vector, src/solve_3d.cc:323-486,729-772).
-  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && !warm_kernel && elastic == 0) {
-    std::vector<int> counts((size_t)B);
-    HIPCHK(c, hipMemcpyAsync(counts.data(), seg_count, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    const int smax = S < BTRAPZ_MAX_SEGMENTS_LONG ? S : BTRAPZ_MAX_SEGMENTS_LONG;
-    std::vector<std::vector<int>> by_count((size_t)smax + 1);
-    size_t n_long = 0;
-    for (int b = 0; b < B; b++)
-      if (counts[b] > BTRAPZ_MAX_SEGMENTS && counts[b] <= smax) { by_count[(size_t)counts[b]].push_back(b); ++n_long; }
-    if (n_long) {
-      if (n_long > c->long_list_cap) {
-        (void)hipFree(c->d_long_list); c->d_long_list = nullptr; c->long_list_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_long_list, sizeof(int) * n_long));
-        c->long_list_cap = n_long;
-      }
-      std::vector<int> flat;
-      flat.reserve(n_long);
-      for (const auto &l : by_count) flat.insert(flat.end(), l.begin(), l.end());
-      HIPCHK(c, hipMemcpyAsync(c->d_long_list, flat.data(), sizeof(int) * n_long, hipMemcpyHostToDevice, stream));
-      HIPCHK(c, hipStreamSynchronize(stream));   // (flat goes out of scope)
-      size_t off = 0;
-      for (int s = BTRAPZ_MAX_SEGMENTS + 1; s <= smax; s++) {
-        const size_t n = by_count[(size_t)s].size();
-        if (!n) continue;
-        KernelArgs l = a;
-        l.S = s; l.order = c->d_long_list + off; l.bucket_S = (int)n; l.seg_count = nullptr; l.cand_prefix = nullptr; l.wave_prefix = nullptr;
-        l.x0 = nullptr; l.lam0 = nullptr; l.lam_out = nullptr; l.x_out = nullptr;
-        hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * (unsigned)n), dim3(64u * (unsigned)((s + 63) / 64)), 0, stream, l, (const double *)c->d_mqm);
-        HIPCHK(c, hipGetLastError());
-        off += n;
-      }
-      c->last_form |= 16;   // (+ 16: the long form served part of a ragged batch)
-    }
-  }
-  hipLaunchKernelGGL(finalize_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, c->d_axis_obj, c->d_axis_status,
-                     c->d_axis_iters, cost, status, iters);
-  HIPCHK(c, hipGetLastError());
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
-  return BTRAPZ_OK;
+  return finalize_and_close(c, s.stream, B, cost, status, iters);
 }
 
 BTRAPZ_EXPORT int btrapz_solve_batch_device(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_options *opt, int B,
@@ -790,8 +871,31 @@ BTRAPZ_EXPORT int btrapz_solve_warm_device(btrapz_ctx *c, const btrapz_shared *s
                       iters, stream);
 }
 
-// The device view of the sets and their M'QM tables (btrapz_solve_sets_device, btrapz_solve_vjp_device), kept by the
-// context and rebuilt, stream-ordered, only when the sets change.
+// ---- entry points that take parameter sets: the sets solve, its VJP and JVP, traj_cost ---------------------------------
+
+static bool sets_in_range(const btrapz_shared *sets, int n_sets) { return sets && n_sets >= 1 && n_sets <= BTRAPZ_MAX_SETS; }
+
+// One launch reads variant and delta from set 0 for every candidate.
+static bool sets_alike(btrapz_ctx *c, const btrapz_shared *sets, int n_sets) {
+  for (int g = 1; g < n_sets; g++)
+    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
+      c->err = "invalid argument: every parameter set must have the same variant and delta";
+      return false;
+    }
+  return true;
+}
+
+// The M'QM table with every weight 1 (the derivative of a table with respect to its weight): built at first use.
+static int unit_mqm_table(btrapz_ctx *c, hipStream_t stream) {
+  if (c->d_mqm_unit.bytes) return BTRAPZ_OK;
+  GROW(c, d_mqm_unit, sizeof(double) * 168);
+  const double ones[4] = {1.0, 1.0, 1.0, 1.0};
+  launch_mqm_table(stream, ones, ones, c->d_mqm_unit);
+  HIPCHK(c, hipGetLastError());
+  return BTRAPZ_OK;
+}
+
+// The device view of the sets and their M'QM tables, kept by the context and rebuilt, stream-ordered, only when the sets change.
 static int sets_tables(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, hipStream_t stream) {
   // the sets as the kernels read them (fill_parameters' limits), padding zeroed so that the cache can compare bytes
   std::vector<Shared> h((size_t)n_sets);
@@ -808,17 +912,17 @@ static int sets_tables(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, hip
         if (c->sets_copy_pending[i]) { HIPCHK(c, hipEventSynchronize(c->sets_copied[i])); c->sets_copy_pending[i] = false; }
         (void)hipHostFree(c->h_sets_stage[i]); c->h_sets_stage[i] = nullptr;
       }
-      (void)hipFree(c->d_sets); (void)hipFree(c->d_mqm_sets);
-      c->d_sets = nullptr; c->d_mqm_sets = nullptr; c->sets_cap = 0;
+      release_all(c->d_sets, c->d_mqm_sets);
+      c->sets_cap = 0;   // (set again once the device tables AND the pinned staging buffers stand)
       const size_t cap = (size_t)BTRAPZ_MAX_SETS < 64 * (((size_t)n_sets + 63) / 64) ? (size_t)BTRAPZ_MAX_SETS : 64 * (((size_t)n_sets + 63) / 64);
-      HIPCHK(c, hipMalloc(&c->d_sets, sizeof(Shared) * cap));
-      HIPCHK(c, hipMalloc(&c->d_mqm_sets, sizeof(double) * 168 * cap));
+      GROW(c, d_sets, sizeof(Shared) * cap);
+      GROW(c, d_mqm_sets, sizeof(double) * 168 * cap);
       for (int i = 0; i < 2; i++) HIPCHK(c, hipHostMalloc((void **)&c->h_sets_stage[i], sizeof(Shared) * cap, hipHostMallocDefault));
       c->sets_cap = cap;
     }
     // Two staging buffers in turn: a buffer is rewritten once ITS copy -- that of the change before the previous one -- has
     // left it.  The copy itself is stream-ordered behind the launches that still read the device tables (same stream, or
-    // the ws_free event above), so a loop whose sets change at every step waits for the device only when it is two
+    // the event of ws_open), so a loop whose sets change at every step waits for the device only when it is two
     // changes ahead of it.
     const int si = c->sets_stage_next;
     c->sets_stage_next = 1 - si;
@@ -840,8 +944,41 @@ static int sets_tables(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, hip
 // on the device by (set, segment count) -- btrapz_sets.hip -- and solved in ONE launch of an ordered instantiation whose
 // wavefronts each hold one set (ipm_solve_*sets*_kernel).  The split form (few candidates) and the long form (65..256
 // segments; the long candidates of a cold ragged batch) hold one candidate per wavefront / workgroup and read its set
-// themselves.  The forms are chosen as solve_common chooses them; the rescue pass, the two-launch solve and the pre-pass
-// are not served here.
+// themselves.  The form comes from choose_form, as for solve_common; the rescue pass, the two-launch solve and the
+// pre-pass are not served here, and the requests are those of btrapz_options (no environment).
+
+// The packed / lean launch of a sets batch: candidates bucketed by key -- set (uniform) or 64 set + 64 - segment count
+// (ragged) -- then one launch over the buckets.
+static int launch_sets_buckets(btrapz_ctx *c, hipStream_t stream, KernelArgs &a, const int *seg_count, const int *set_index,
+                               int n_sets, bool lean_on, bool warm_kernel) {
+  const int B = a.B, S = a.S;
+  const int n_keys = (seg_count ? 64 : 1) * n_sets;
+  const size_t meta_need = 3 * (size_t)n_keys + 2;
+  GROW(c, d_sets_meta, sizeof(int) * meta_need);
+  GROW(c, d_order, sizeof(int) * (size_t)B);
+  int *meta = c->d_sets_meta;
+  HIPCHK(c, hipMemsetAsync(meta + 2 * ((size_t)n_keys + 1), 0, sizeof(int) * (size_t)n_keys, stream));
+  const unsigned nb = (unsigned)((B + 255) / 256);
+  hipLaunchKernelGGL(sets_hist_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, set_index, n_sets, n_keys, meta);
+  hipLaunchKernelGGL(sets_prefix_kernel, dim3(1), dim3(1024), 0, stream, n_keys, seg_count ? 0 : S, meta);
+  hipLaunchKernelGGL(sets_scatter_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, set_index, n_sets, n_keys, meta,
+                     c->d_order, c->d_axis_obj, c->d_axis_status, c->d_axis_iters);
+  HIPCHK(c, hipGetLastError());
+  a.order = c->d_order; a.seg_count = seg_count; a.cand_prefix = meta; a.wave_prefix = meta + n_keys + 1;
+  a.bucket_S = seg_count ? 0 : S;
+  // Upper bound on the wavefront pairs without a host round trip: a key of n candidates needs ceil(n / gpw) pairs, less
+  // than n / gpw + 1, and at most min(n_keys, B) keys are non-empty.  Ragged batches (gpw >= 1): at most 2 B + 2 pairs
+  // against the ragged path's B + 65 -- the surplus wavefronts find no bucket in their binary search and leave.
+  const int gpw_min = seg_count ? 1 : 64 / S;
+  const unsigned blocks = 2u * (unsigned)((size_t)B / (size_t)gpw_min + (size_t)(n_keys < B ? n_keys : B) + 1);
+  auto kernel = lean_on ? (warm_kernel ? ipm_solve_lean_sets_warm_ordered_kernel : ipm_solve_lean_sets_ordered_kernel)
+                        : (warm_kernel ? ipm_solve_sets_warm_ordered_kernel : ipm_solve_sets_ordered_kernel);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, a, (const double *)c->d_mqm_sets, (const Shared *)c->d_sets, n_keys);
+  HIPCHK(c, hipGetLastError());
+  c->last_form = lean_on ? 8 : 0;
+  return BTRAPZ_OK;
+}
+
 BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
                                         const btrapz_options *opt, const btrapz_warm *warm, int B, int seg_stride,
                                         const double *seg, const int *seg_count, const double *init, const double *ref_end,
@@ -849,7 +986,7 @@ BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *s
                                         void *stream_) {
   if (!c) return BTRAPZ_EINVAL;
   const int S = seg_stride;
-  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS || !set_index || B < 1 || S < 1 || !seg || !init || !ref_end ||
+  if (!sets_in_range(sets, n_sets) || !set_index || B < 1 || S < 1 || !seg || !init || !ref_end ||
       !dl_bounds || !ctrl || !cost || !status) {
     c->err = "invalid argument (sets: 1 <= n_sets <= BTRAPZ_MAX_SETS, set_index and the batch arrays non-null, B >= 1)";
     return BTRAPZ_EINVAL;
@@ -860,135 +997,52 @@ BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *s
     return BTRAPZ_EINVAL;
   }
   const bool warm_args = warm && (warm->x0 || warm->lam0 || warm->lam_out);
-  const bool long_form = !seg_count && S > BTRAPZ_MAX_SEGMENTS;
-  if (long_form && warm_args) {
+  if (!seg_count && S > BTRAPZ_MAX_SEGMENTS && warm_args) {
     c->err = "more than 64 segments: uniform cold solve only";
     return BTRAPZ_EINVAL;
   }
-  for (int g = 1; g < n_sets; g++)
-    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
-      c->err = "invalid argument: every parameter set must have the same variant and delta";
-      return BTRAPZ_EINVAL;
-    }
+  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
   if (opt && (opt->elastic != 0 || opt->cap_iter > 0 || opt->compact > 0 || opt->queue > 0 || opt->start != 0)) {
     c->err = "invalid argument: with parameter sets, elastic, cap_iter > 0, compact = 1, queue and start are not served";
     return BTRAPZ_EINVAL;
   }
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
-  int rc = ensure_axis_ws(c, 2 * (size_t)B);
-  if (rc != BTRAPZ_OK) return rc;
-  rc = sets_tables(c, sets, n_sets, stream);
-  if (rc != BTRAPZ_OK) return rc;
+  TRY(ws_open(c, stream));
+  TRY(ensure_axis_ws(c, 2 * (size_t)B));
+  TRY(sets_tables(c, sets, n_sets, stream));
   KernelArgs a;
   fill_parameters(a, &sets[0], opt, warm);   // (a.sh is not read: every wavefront reads its own set)
-  a.B = B; a.S = S; a.seg_stride = S;
-  a.order = nullptr; a.seg_count = nullptr; a.cand_prefix = nullptr; a.wave_prefix = nullptr;
-  a.seg = seg; a.init = init; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.mqm = c->d_mqm_sets;
-  a.ctrl = ctrl; a.axis_obj = c->d_axis_obj; a.axis_status = c->d_axis_status; a.axis_iters = c->d_axis_iters;
-  a.axis_viol = c->d_axis_viol; c->viol_valid = 0;
-  a.x_out = nullptr; a.queue = c->d_queue;
+  batch_arguments(c, a, B, S, seg, init, ref_end, dl_bounds, ctrl, c->d_mqm_sets);
   const bool warm_kernel = a.x0 || a.lam0 || a.lam_out;
-  const double *mq = c->d_mqm_sets;
-  const Shared *dsets = c->d_sets;
-  // the form, as solve_common chooses it for one launch: the split form while 2 B wavefronts fit the device's SIMDs at once
-  // (uniform cold batches of at most 21 segments), two wavefronts per SIMD for batches of >= 1.25 wavefronts per SIMD
-  const int split_opt = opt ? opt->split : 0;
-  const bool split_on = !seg_count && !warm_kernel && S <= 21 &&
-                        (split_opt > 0 || (split_opt == 0 && 2u * (unsigned)B <= (unsigned)c->resident_waves));
-  if (long_form) {
+  const double *mq = c->d_mqm_sets; const Shared *dsets = c->d_sets;
+  // (ordered: a ragged batch always goes through the bucket list, a uniform one may take the split form; one launch:
+  //  cap_iter = -1, and blocks -- which only the automatic two launches look at -- is not known yet)
+  FormQuery q{};
+  q.B = B; q.S = S; q.ragged = seg_count != nullptr; q.warm_kernel = warm_kernel; q.ordered = seg_count != nullptr; q.compact = false;
+  q.elastic = 0; q.max_iter = a.max_iter; q.split = opt ? opt->split : 0; q.lean = opt ? opt->lean : 0; q.cap_iter = -1; q.queue = false;
+  q.unc_start = a.unc_start; q.resident_waves = c->resident_waves; q.blocks = 0;
+  const Form f = choose_form(q);
+  if (f.long_form) {
     c->last_form = 2;
     hipLaunchKernelGGL(ipm_solve_long_sets_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, stream, a,
                        mq, dsets, set_index, n_sets);
     HIPCHK(c, hipGetLastError());
-  } else if (split_on) {
+  } else if (f.split_on) {
     c->last_form = 1;
     hipLaunchKernelGGL(ipm_solve_sets_split_kernel, dim3(2u * (unsigned)B), dim3(64), 0, stream, a, mq, dsets, set_index, n_sets);
     HIPCHK(c, hipGetLastError());
   } else {
-    // bucket the candidates by key: set (uniform) or 64 set + 64 - segment count (ragged)
-    const int n_keys = (seg_count ? 64 : 1) * n_sets;
-    const size_t meta_need = 3 * (size_t)n_keys + 2;
-    if (meta_need > c->sets_meta_cap) {
-      (void)hipFree(c->d_sets_meta); c->d_sets_meta = nullptr; c->sets_meta_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_sets_meta, sizeof(int) * meta_need));
-      c->sets_meta_cap = meta_need;
-    }
-    if ((size_t)B > c->order_cap) {
-      (void)hipFree(c->d_order); c->d_order = nullptr; c->order_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_order, sizeof(int) * (size_t)B));
-      c->order_cap = B;
-    }
-    int *meta = c->d_sets_meta;
-    HIPCHK(c, hipMemsetAsync(meta + 2 * ((size_t)n_keys + 1), 0, sizeof(int) * (size_t)n_keys, stream));
-    const unsigned nb = (unsigned)((B + 255) / 256);
-    hipLaunchKernelGGL(sets_hist_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, set_index, n_sets, n_keys, meta);
-    hipLaunchKernelGGL(sets_prefix_kernel, dim3(1), dim3(1024), 0, stream, n_keys, seg_count ? 0 : S, meta);
-    hipLaunchKernelGGL(sets_scatter_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, set_index, n_sets, n_keys, meta,
-                       c->d_order, c->d_axis_obj, c->d_axis_status, c->d_axis_iters);
-    HIPCHK(c, hipGetLastError());
-    a.order = c->d_order; a.seg_count = seg_count; a.cand_prefix = meta; a.wave_prefix = meta + n_keys + 1;
-    a.bucket_S = seg_count ? 0 : S;
-    const int lean_opt = opt ? opt->lean : 0;
-    const unsigned est_waves = 2u * (unsigned)((size_t)B / (size_t)(64 / (S < 64 ? S : 64)) + 1);
-    // (slots for more than 64 segments: the packed form, as solve_common chooses it for such a ragged batch)
-    const bool lean_ok = (S >= 3 || seg_count) && S <= BTRAPZ_MAX_SEGMENTS && a.unc_start == 0;
-    const bool lean_on = lean_ok && (lean_opt > 0 || (lean_opt == 0 && 4u * est_waves >= 5u * (unsigned)c->resident_waves));
-    // Upper bound on the wavefront pairs without a host round trip: a key of n candidates needs ceil(n / gpw) pairs, less
-    // than n / gpw + 1, and at most min(n_keys, B) keys are non-empty.  Ragged batches (gpw >= 1): at most 2 B + 2 pairs
-    // against the ragged path's B + 65 -- the surplus wavefronts find no bucket in their binary search and leave.
-    const int gpw_min = seg_count ? 1 : 64 / S;
-    const unsigned blocks = 2u * (unsigned)((size_t)B / (size_t)gpw_min + (size_t)(n_keys < B ? n_keys : B) + 1);
-    auto kernel = lean_on ? (warm_kernel ? ipm_solve_lean_sets_warm_ordered_kernel : ipm_solve_lean_sets_ordered_kernel)
-                          : (warm_kernel ? ipm_solve_sets_warm_ordered_kernel : ipm_solve_sets_ordered_kernel);
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, a, mq, dsets, n_keys);
-    HIPCHK(c, hipGetLastError());
-    c->last_form = lean_on ? 8 : 0;
+    TRY(launch_sets_buckets(c, stream, a, seg_count, set_index, n_sets, f.lean_on, warm_kernel));
   }
-  // Cold ragged batch with slots for more than 64 segments: the candidates that HAVE more than 64 (the bucket kernels marked
-  // them "no usable corridor") are solved by the long form, as solve_common does it -- their counts come to the host, one
-  // launch per count over a list; each workgroup reads its candidate's set (warm starts keep them unsolved, as there).
+  // Cold ragged batch with slots for more than 64 segments: its long candidates, each workgroup reading its candidate's
+  // set (warm starts keep them unsolved, as in solve_common).
   if (seg_count && S > BTRAPZ_MAX_SEGMENTS && !warm_kernel) {
-    std::vector<int> counts((size_t)B);
-    HIPCHK(c, hipMemcpyAsync(counts.data(), seg_count, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    const int smax = S < BTRAPZ_MAX_SEGMENTS_LONG ? S : BTRAPZ_MAX_SEGMENTS_LONG;
-    std::vector<std::vector<int>> by_count((size_t)smax + 1);
-    size_t n_long = 0;
-    for (int b = 0; b < B; b++)
-      if (counts[b] > BTRAPZ_MAX_SEGMENTS && counts[b] <= smax) { by_count[(size_t)counts[b]].push_back(b); ++n_long; }
-    if (n_long) {
-      if (n_long > c->long_list_cap) {
-        (void)hipFree(c->d_long_list); c->d_long_list = nullptr; c->long_list_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_long_list, sizeof(int) * n_long));
-        c->long_list_cap = n_long;
-      }
-      std::vector<int> flat;
-      flat.reserve(n_long);
-      for (const auto &l : by_count) flat.insert(flat.end(), l.begin(), l.end());
-      HIPCHK(c, hipMemcpyAsync(c->d_long_list, flat.data(), sizeof(int) * n_long, hipMemcpyHostToDevice, stream));
-      HIPCHK(c, hipStreamSynchronize(stream));   // (flat goes out of scope)
-      size_t off = 0;
-      for (int s = BTRAPZ_MAX_SEGMENTS + 1; s <= smax; s++) {
-        const size_t n = by_count[(size_t)s].size();
-        if (!n) continue;
-        KernelArgs l = a;
-        l.S = s; l.order = c->d_long_list + off; l.bucket_S = (int)n; l.seg_count = nullptr; l.cand_prefix = nullptr; l.wave_prefix = nullptr;
-        hipLaunchKernelGGL(ipm_solve_long_sets_kernel, dim3(2u * (unsigned)n), dim3(64u * (unsigned)((s + 63) / 64)), 0, stream, l,
-                           mq, dsets, set_index, n_sets);
-        HIPCHK(c, hipGetLastError());
-        off += n;
-      }
-      c->last_form |= 16;
-    }
+    auto launch = [&](const KernelArgs &l, unsigned n, int segs) {
+      hipLaunchKernelGGL(ipm_solve_long_sets_kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, stream, l, mq, dsets, set_index, n_sets);
+    };
+    TRY(solve_long_candidates(c, stream, a, seg_count, launch));
   }
-  hipLaunchKernelGGL(finalize_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, c->d_axis_obj, c->d_axis_status,
-                     c->d_axis_iters, cost, status, iters);
-  HIPCHK(c, hipGetLastError());
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
-  return BTRAPZ_OK;
+  return finalize_and_close(c, stream, B, cost, status, iters);
 }
 
 // Gradients of a solve (btrapz_solve_vjp_device): one launch of vjp_kernel (btrapz_vjp.hip), groups of S lanes as the
@@ -1000,7 +1054,7 @@ BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *se
                                        const btrapz_grads *out, void *stream_) {
   (void)init;   // (the initial state enters the gradient through the returned control points of segment 0)
   if (!c) return BTRAPZ_EINVAL;
-  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds || !out) {
+  if (!sets_in_range(sets, n_sets) || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds || !out) {
     c->err = "invalid argument (vjp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays and out non-null)";
     return BTRAPZ_EINVAL;
   }
@@ -1016,24 +1070,11 @@ BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *se
     c->err = "invalid argument: vjp needs ctrl_bar or cost_bar (both NULL)";
     return BTRAPZ_EINVAL;
   }
-  for (int g = 1; g < n_sets; g++)
-    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
-      c->err = "invalid argument: every parameter set must have the same variant and delta";
-      return BTRAPZ_EINVAL;
-    }
+  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
-  int rc = sets_tables(c, sets, n_sets, stream);
-  if (rc != BTRAPZ_OK) return rc;
-  if (!c->d_mqm_unit) {
-    HIPCHK(c, hipMalloc(&c->d_mqm_unit, sizeof(double) * 168));
-    MqmWeights ones;
-    for (int ax = 0; ax < 2; ax++)
-      for (int d = 0; d < 4; d++) ones.w[ax][d] = 1.0;
-    hipLaunchKernelGGL(mqm_table_kernel, dim3(1), dim3(192), 0, stream, ones, c->d_mqm_unit);
-    HIPCHK(c, hipGetLastError());
-  }
+  TRY(ws_open(c, stream));
+  TRY(sets_tables(c, sets, n_sets, stream));
+  TRY(unit_mqm_table(c, stream));
   VjpArgs a;
   a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.seg_count = seg_count;
   a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
@@ -1044,9 +1085,7 @@ BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *se
   const unsigned blocks = 2u * (unsigned)(((size_t)B + gpw - 1) / gpw);
   hipLaunchKernelGGL(vjp_kernel, dim3(blocks), dim3(64), 0, stream, a);
   HIPCHK(c, hipGetLastError());
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 // Directional derivatives of a solve (btrapz_solve_jvp_device): one launch of jvp_kernel (btrapz_jvp.hip), vjp_kernel's
@@ -1058,7 +1097,7 @@ BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *se
                                        double *cost_dot, void *stream_) {
   (void)init;   // (the tangent system is stated at the returned control points; init_dot is what moves them)
   if (!c) return BTRAPZ_EINVAL;
-  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds) {
+  if (!sets_in_range(sets, n_sets) || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds) {
     c->err = "invalid argument (jvp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays non-null)";
     return BTRAPZ_EINVAL;
   }
@@ -1082,24 +1121,11 @@ BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *se
     c->err = "invalid argument: jvp of 1 <= T <= BTRAPZ_MAX_TANGENTS tangents per call";
     return BTRAPZ_EINVAL;
   }
-  for (int g = 1; g < n_sets; g++)
-    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
-      c->err = "invalid argument: every parameter set must have the same variant and delta";
-      return BTRAPZ_EINVAL;
-    }
+  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
-  int rc = sets_tables(c, sets, n_sets, stream);
-  if (rc != BTRAPZ_OK) return rc;
-  if (!c->d_mqm_unit) {   // (as btrapz_solve_vjp_device builds it)
-    HIPCHK(c, hipMalloc(&c->d_mqm_unit, sizeof(double) * 168));
-    MqmWeights ones;
-    for (int ax = 0; ax < 2; ax++)
-      for (int d = 0; d < 4; d++) ones.w[ax][d] = 1.0;
-    hipLaunchKernelGGL(mqm_table_kernel, dim3(1), dim3(192), 0, stream, ones, c->d_mqm_unit);
-    HIPCHK(c, hipGetLastError());
-  }
+  TRY(ws_open(c, stream));
+  TRY(sets_tables(c, sets, n_sets, stream));
+  TRY(unit_mqm_table(c, stream));
   JvpArgs a;
   a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.T = T; a.seg_count = seg_count;
   a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
@@ -1110,9 +1136,7 @@ BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *se
   const unsigned blocks = (unsigned)(((size_t)B + gpw - 1) / gpw);
   hipLaunchKernelGGL(jvp_kernel, dim3(blocks), dim3(128), 0, stream, a);
   HIPCHK(c, hipGetLastError());
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 // a_cost of sampled trajectories and its VJP (btrapz_traj_cost_device, btrapz_traj_cost_vjp_device): one workgroup of 64
@@ -1123,7 +1147,7 @@ static int traj_cost_common(btrapz_ctx *c, bool vjp, const btrapz_shared *sets, 
                             double *a_cost, int *n_points, const double *a_cost_bar, double *ctrl_bar, double *init_bar,
                             double *params_bar, double *s_ref_bar, double *l_ref_bar, void *stream_) {
   if (!c) return BTRAPZ_EINVAL;
-  if (!sets || n_sets < 1 || n_sets > BTRAPZ_MAX_SETS) {
+  if (!sets_in_range(sets, n_sets)) {
     c->err = "invalid argument: 1 <= n_sets <= BTRAPZ_MAX_SETS and sets non-null";
     return BTRAPZ_EINVAL;
   }
@@ -1139,11 +1163,7 @@ static int traj_cost_common(btrapz_ctx *c, bool vjp, const btrapz_shared *sets, 
     c->err = "invalid argument: seg_stride > BTRAPZ_MAX_SEGMENTS_LONG";
     return BTRAPZ_EINVAL;
   }
-  for (int g = 1; g < n_sets; g++)
-    if (sets[g].variant != sets[0].variant || !(sets[g].delta == sets[0].delta)) {
-      c->err = "invalid argument: every parameter set must have the same variant and delta";
-      return BTRAPZ_EINVAL;
-    }
+  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
   if (sets[0].variant != BTRAPZ_TRAPEZOID && sets[0].variant != BTRAPZ_CUBOID) {
     c->err = "invalid argument: variant";
     return BTRAPZ_EINVAL;
@@ -1161,10 +1181,8 @@ static int traj_cost_common(btrapz_ctx *c, bool vjp, const btrapz_shared *sets, 
     return BTRAPZ_EINVAL;
   }
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
-  int rc = sets_tables(c, sets, n_sets, stream);
-  if (rc != BTRAPZ_OK) return rc;
+  TRY(ws_open(c, stream));
+  TRY(sets_tables(c, sets, n_sets, stream));
   AcostArgs a;
   a.B = B; a.seg_stride = seg_stride; a.seg_count = seg_count;
   a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index;
@@ -1176,9 +1194,7 @@ static int traj_cost_common(btrapz_ctx *c, bool vjp, const btrapz_shared *sets, 
   if (vjp) hipLaunchKernelGGL(acost_vjp_kernel, dim3((unsigned)B), dim3(64), 0, stream, a);
   else hipLaunchKernelGGL(acost_kernel, dim3((unsigned)B), dim3(64), 0, stream, a);
   HIPCHK(c, hipGetLastError());
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 BTRAPZ_EXPORT int btrapz_traj_cost_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index, int B,
@@ -1274,9 +1290,8 @@ BTRAPZ_EXPORT int btrapz_rescue_violations_device(btrapz_ctx *c, int B, double *
   if (!c) return BTRAPZ_EINVAL;
   if (B < 1 || !viol) { c->err = "invalid argument"; return BTRAPZ_EINVAL; }
   if ((size_t)B != c->viol_valid) { c->err = "the context's last solve of B candidates had no rescue pass (btrapz_options.elastic)"; return BTRAPZ_EINVAL; }
-  HIPCHK(c, hipSetDevice(c->device));
   hipStream_t stream = (hipStream_t)stream_;
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  TRY(ws_open(c, stream));   // (it reads the last solve's records and writes no workspace: nothing to close)
   hipLaunchKernelGGL(rescue_violations_kernel, dim3((4 * B + 255) / 256), dim3(256), 0, stream, B, (const double *)c->d_axis_viol, viol);
   HIPCHK(c, hipGetLastError());
   return BTRAPZ_OK;
@@ -1321,20 +1336,14 @@ static int launch_corridor_serial(btrapz_ctx *c, CorridorArgs a, hipStream_t str
     if (cap_sel < 2 * (size_t)a.seg_stride + 16) cap_sel = 2 * (size_t)a.seg_stride + 16;
   }
   const size_t need = (B * O * cap_o + B * cap_sel) * seg_bytes;
-  if (need > c->corr_ws_cap) {
-    (void)hipFree(c->d_corr_ws); c->d_corr_ws = nullptr; c->corr_ws_cap = 0;
-    if (hipMalloc(&c->d_corr_ws, need) != hipSuccess) { (void)hipGetLastError(); c->err = "corridor stage: no memory for the segment lists of this horizon"; return BTRAPZ_ENOMEM; }
-    c->corr_ws_cap = need;
-  }
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+  if (c->d_corr_ws.grow(need) != hipSuccess) { (void)hipGetLastError(); c->err = "corridor stage: no memory for the segment lists of this horizon"; return BTRAPZ_ENOMEM; }
+  TRY(ws_wait(c, stream));
   a.cap_o = (int)cap_o; a.cap_sel = (int)cap_sel; a.pass = 0; a.retry_list = nullptr; a.retry_count = nullptr;
-  Seg *all = reinterpret_cast<Seg *>(c->d_corr_ws);
-  Seg *sel = reinterpret_cast<Seg *>(reinterpret_cast<char *>(c->d_corr_ws) + B * O * cap_o * seg_bytes);
+  Seg *all = reinterpret_cast<Seg *>(c->d_corr_ws.ptr());
+  Seg *sel = reinterpret_cast<Seg *>(c->d_corr_ws.ptr() + B * O * cap_o * seg_bytes);
   hipLaunchKernelGGL(corridor_serial_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, a, all, sel);
   HIPCHK(c, hipGetLastError());
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 static int launch_corridor_stage(btrapz_ctx *c, CorridorArgs a, bool prisms, hipStream_t stream) {
@@ -1342,11 +1351,7 @@ static int launch_corridor_stage(btrapz_ctx *c, CorridorArgs a, bool prisms, hip
   if (!prisms && (N > 512 || num_obs > 64)) return launch_corridor_serial(c, a, stream);
   // Two passes (corridor_kernels.hip): lists sized for the usual case first -- LDS per workgroup is what limits the
   // wavefronts per CU -- then the candidates that overflowed them, with the full capacities.
-  if ((size_t)B + 1 > c->retry_cap) {
-    (void)hipFree(c->d_retry); c->d_retry = nullptr; c->retry_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_retry, sizeof(int) * ((size_t)B + 1)));
-    c->retry_cap = (size_t)B + 1;
-  }
+  GROW(c, d_retry, sizeof(int) * ((size_t)B + 1));
   HIPCHK(c, hipMemsetAsync(c->d_retry, 0, sizeof(int), stream));
   a.retry_count = c->d_retry; a.retry_list = c->d_retry + 1;
   const int cap_o_big = 160 / num_obs, cap_sel_big = 64;        // MAX_ALL / O, MAX_SEL of corridor_kernels.hip
@@ -1448,20 +1453,14 @@ BTRAPZ_EXPORT int btrapz_prism_corridor_batch_device(btrapz_ctx *c, int variant,
     return launch_corridor_stage(c, a, true, stream);
   }
   const size_t need = sizeof(double) * 4 * (size_t)B * O * N + sizeof(int) * (size_t)B;
-  if (need > c->strip_cap) {
-    (void)hipFree(c->d_strips); c->d_strips = nullptr; c->strip_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_strips, need));
-    c->strip_cap = need;
-  }
-  if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
-  double *sb = reinterpret_cast<double *>(c->d_strips), *lb = sb + 2 * (size_t)B * O * N;
+  GROW(c, d_strips, need);
+  TRY(ws_wait(c, stream));
+  double *sb = reinterpret_cast<double *>(c->d_strips.ptr()), *lb = sb + 2 * (size_t)B * O * N;
   int *ns = n_strips ? n_strips : reinterpret_cast<int *>(lb + 2 * (size_t)B * O * N);
-  const int rc = btrapz_prism_bounds_device(c, B, P, N, road, prisms, O, sb, lb, ns, stream_);
-  if (rc != BTRAPZ_OK) return rc;
+  TRY(btrapz_prism_bounds_device(c, B, P, N, road, prisms, O, sb, lb, ns, stream_));
   a.s_bounds = sb; a.l_bounds = lb;
   const int rc2 = launch_corridor_stage(c, a, false, stream);
-  c->ws_stream = stream; c->ws_used = true;
-  HIPCHK(c, hipEventRecord(c->ws_free, stream));
+  TRY(ws_close(c, stream));
   return rc2;
 }
 
@@ -1477,22 +1476,19 @@ BTRAPZ_EXPORT int btrapz_argmin_device(btrapz_ctx *c, int B, int group, long lon
   if (chunks > 256) chunks = 256;
   if (chunks > 1) {
     const size_t need = (size_t)groups * chunks;
-    if (need > c->argmin_cap) {
-      (void)hipFree(c->d_argmin_cost); (void)hipFree(c->d_argmin_idx);
-      c->d_argmin_cost = nullptr; c->d_argmin_idx = nullptr; c->argmin_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_argmin_cost, sizeof(double) * need));
-      HIPCHK(c, hipMalloc(&c->d_argmin_idx, sizeof(long long) * need));
-      c->argmin_cap = need;
+    if (need > c->d_argmin_idx.cap()) {
+      release_all(c->d_argmin_cost, c->d_argmin_idx);
+      GROW(c, d_argmin_cost, sizeof(double) * need);
+      GROW(c, d_argmin_idx, sizeof(long long) * need);
     }
-    if (c->ws_used && stream != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(stream, c->ws_free, 0));
+    TRY(ws_wait(c, stream));
   }
   hipLaunchKernelGGL(argmin_kernel, dim3(groups, chunks), dim3(256), 0, stream, group, index_base, cost, best_idx, best_cost,
-                     c->d_argmin_cost, c->d_argmin_idx);
+                     c->d_argmin_cost.ptr(), c->d_argmin_idx.ptr());
   if (chunks > 1) {
     hipLaunchKernelGGL(argmin_final_kernel, dim3(groups), dim3(256), 0, stream, chunks, index_base,
                        (const double *)c->d_argmin_cost, (const long long *)c->d_argmin_idx, best_idx, best_cost);
-    c->ws_stream = stream; c->ws_used = true;
-    HIPCHK(c, hipEventRecord(c->ws_free, stream));
+    TRY(ws_close(c, stream));
   }
   HIPCHK(c, hipGetLastError());
   return BTRAPZ_OK;
@@ -1548,16 +1544,8 @@ BTRAPZ_EXPORT int btrapz_solve_batch_host(btrapz_ctx *c, const btrapz_shared *sh
   const size_t n_seg = (size_t)BTRAPZ_NUM_SEG_FIELDS * B * S, n_init = (size_t)B * 6, n_re = (size_t)B * 2, n_dl = (size_t)B * 10;
   const size_t n_ctrl = (size_t)B * 12 * S, n_cost = B;
   const size_t need = n_seg + n_init + n_re + n_dl + n_ctrl + n_cost;
-  if (need > c->stage_cap) {
-    (void)hipFree(c->d_stage); c->d_stage = nullptr; c->stage_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_stage, sizeof(double) * need));
-    c->stage_cap = need;
-  }
-  if ((size_t)2 * B > c->istage_cap) {
-    (void)hipFree(c->d_istage); c->d_istage = nullptr; c->istage_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_istage, sizeof(int) * 2 * (size_t)B));
-    c->istage_cap = 2 * (size_t)B;
-  }
+  GROW(c, d_stage, sizeof(double) * need);
+  GROW(c, d_istage, sizeof(int) * 2 * (size_t)B);
   double *d_seg = c->d_stage, *d_init = d_seg + n_seg, *d_re = d_init + n_init, *d_dl = d_re + n_re;
   double *d_ctrl = d_dl + n_dl, *d_cost = d_ctrl + n_ctrl;
   int *d_status = c->d_istage, *d_iters = c->d_istage + B;
@@ -1565,8 +1553,7 @@ BTRAPZ_EXPORT int btrapz_solve_batch_host(btrapz_ctx *c, const btrapz_shared *sh
   HIPCHK(c, hipMemcpy(d_init, init, sizeof(double) * n_init, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(d_re, ref_end, sizeof(double) * n_re, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(d_dl, dl_bounds, sizeof(double) * n_dl, hipMemcpyHostToDevice));
-  int rc = btrapz_solve_batch_device(c, sh, opt, B, S, d_seg, d_init, d_re, d_dl, d_ctrl, d_cost, d_status, d_iters, nullptr);
-  if (rc != BTRAPZ_OK) return rc;
+  TRY(btrapz_solve_batch_device(c, sh, opt, B, S, d_seg, d_init, d_re, d_dl, d_ctrl, d_cost, d_status, d_iters, nullptr));
   HIPCHK(c, hipDeviceSynchronize());
   HIPCHK(c, hipMemcpy(ctrl, d_ctrl, sizeof(double) * n_ctrl, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(cost, d_cost, sizeof(double) * n_cost, hipMemcpyDeviceToHost));
