@@ -427,6 +427,59 @@ int btrapz_corridor_batch_device(btrapz_ctx *ctx, int variant, int B, int N, int
                                  double *seg, int *seg_count, double *ref_end, double *dl_bounds,
                                  void *stream);
 
+/* ---- gradients of the corridor stage w.r.t. the per-knot bounds and reference lines -------------------------------------
+ * The backward pass of btrapz_corridor_batch_device: given cotangents of its outputs (seg, ref_end, dl_bounds) it writes
+ * the gradients w.r.t. its six input arrays.  Asynchronous and stream-ordered, no host round trip; it takes nothing from
+ * the forward call but its inputs and makes the stage's decisions again itself, bit for bit (same statements).
+ * With those decisions frozen -- where a segment opens, which segments are selected, their order and final spans -- the
+ * stage is a sparse linear map, and this is its exact transpose.  Let output segment k of a candidate come from obstacle o,
+ * its base segment opened at knot i0, h one-second pieces split off in front of it; lo / hi the obstacle's s bounds,
+ * llo / lhi its l bounds, d = delta:
+ *   down_skew = (lo(i0+1) - lo(i0)) / d, down_bias = lo(i0) + h down_skew:
+ *       lo(i0)   gets down_bias_bar (1 - h/d) - down_skew_bar / d,  lo(i0+1) gets (h down_bias_bar + down_skew_bar) / d;
+ *       upp_* the same with hi.
+ *   trapezoid (variant 0): l_down_bias = llo(i0); l_down_skew = (llo(1) - llo(0)) / d for i0 = 0, else
+ *       (llo(i0) - llo(i0-1)) / d; pieces inherit both; l_upp_* with lhi.  Cuboid: the four fields are defaults, no gradient.
+ *   beg_l = llo(i0), end_l = lhi(i0).
+ *   ds_lo / ds_hi: max / min of ds_bounds over the FINAL span beg_t..end_t (after the overlap step, indices clamped to
+ *       [0, N-1]): the gradient goes to the EARLIEST knot of the span that attains it; where the default (0 / 1000)
+ *       attains it, to nobody.
+ *   x_skew, x_bias, y_skew, y_bias read s_ref / l_ref at min(10 k, N-1) and min(10 k + 1, N-1).
+ *   field 0 (T) is an integer knot count times delta: not differentiated, its cotangent is ignored.
+ *   ref_end -> s_ref[N-1], l_ref[N-1];  dl_bounds[2 i + j] -> dl_bounds_knots[min(i, N-1)][j], i = 0..4.
+ *   The role of s_ref / l_ref in the SELECTION is a decision, not a derivative: they get gradients through the x / y
+ *   fields and ref_end only.
+ *   A candidate whose forward seg_count is 0 or -1 gets 0 in every entry.  Cotangents of slots >= seg_count are ignored.
+ *   Where the de-dup removed a twin, the gradient goes to the copy the forward kept (the first).
+ *   Every output is OVERWRITTEN (entries nothing reaches: 0), never accumulated into.  Sums into one entry are taken in
+ *   ascending segment order: the same inputs give the same bits on every run.
+ * Cotangents: seg_bar [NUM_SEG_FIELDS][B][seg_stride], ref_end_bar [B][2], dl_bounds_bar [B][10]; any may be NULL (zero).
+ * Refused (BTRAPZ_EINVAL, btrapz_last_error says why): a shape beyond the wave-wide kernels -- N > 512, num_obs > 64 or
+ * seg_stride > BTRAPZ_MAX_SEGMENTS (the one-lane-per-candidate path of the forward is not differentiated); an input
+ * pointer NULL; all three cotangents NULL; `out` NULL or every output NULL; B < 1, N < 3, num_obs < 1, delta not > 0. */
+typedef struct btrapz_knot_grads {   /* DEVICE pointers, overwritten; any may be NULL (not wanted), not all */
+  double *s_bounds;         /* [B][num_obs][N][2] */
+  double *l_bounds;         /* [B][num_obs][N][2] */
+  double *ds_bounds;        /* [B][N][2] */
+  double *dl_bounds_knots;  /* [B][N][2] */
+  double *s_ref, *l_ref;    /* [B][N] */
+} btrapz_knot_grads;
+
+int btrapz_corridor_batch_vjp_device(btrapz_ctx *ctx, int variant, int B, int N, int num_obs, double delta,
+                                     const double *s_bounds, const double *l_bounds, const double *ds_bounds,
+                                     const double *dl_bounds_knots, const double *s_ref, const double *l_ref,
+                                     int seg_stride, const double *seg_bar, const double *ref_end_bar,
+                                     const double *dl_bounds_bar, const btrapz_knot_grads *out, void *stream);
+
+/* The same for ONE candidate on the host (no GPU, no context): every pointer a host pointer, B = 1, the pointers of `out`
+ * host pointers too; *seg_count (may be NULL) receives the forward's count.  Same decisions, same rules, same order of
+ * the sums as the device call.  Returns BTRAPZ_OK or BTRAPZ_EINVAL (the refusals above). */
+int btrapz_corridor_vjp_host(int variant, int N, int num_obs, double delta, const double *s_bounds,
+                             const double *l_bounds, const double *ds_bounds, const double *dl_bounds_knots,
+                             const double *s_ref, const double *l_ref, int seg_stride, const double *seg_bar,
+                             const double *ref_end_bar, const double *dl_bounds_bar, const btrapz_knot_grads *out,
+                             int *seg_count);
+
 /* ---- obstacle prisms -> per-knot bounds -------------------------------------------------------
  * The scene logic in front of the corridor text file, for B scenes at once: Car.getCar + get_bounds of the reference's
  * harness (src/cart_frenet.py:664-1030, lineFromPoints :818-830).  A car is a prism in (s, l, t): centre (s0, l0, t0),

@@ -197,6 +197,37 @@ __global__ void prism_corridor_first_kernel(const CorridorArgs a, int staged);
 __global__ void prism_corridor_first_short_kernel(const CorridorArgs a, int staged);
 struct Seg;
 __global__ void corridor_serial_kernel(const CorridorArgs a, Seg *ws_all, Seg *ws_sel);   // beyond the wave-wide kernels' limits: one lane per candidate
+// btrapz_corridor_batch_vjp_device (corridor_vjp.hip): the backward pass of the wave-wide corridor stage, one wavefront per
+// candidate; the forward's two-pass pattern (pass, cap_o, cap_sel, retry list as in CorridorArgs)
+struct CorridorVjpArgs {
+  int B, N, num_obs, variant, seg_stride;
+  double delta;
+  const double *s_bounds, *l_bounds, *ds_bounds, *s_ref, *l_ref;
+  const double *seg_bar, *ref_end_bar, *dl10_bar;   // cotangents, any may be null
+  btrapz_knot_grads out;                            // zeroed in front of the launch; any may be null
+  int cap_o, cap_sel, pass, staged;                 // staged: the slope table fits LDS
+  int *retry_list, *retry_count;
+};
+constexpr int kCorridorVjpTerms = 16;               // terms an output segment stages (corridor_vjp_core.h: 4 + 6 + 2 + 2 + 2)
+// Dynamic LDS of corridor_vjp_kernel, byte offsets (the host sizes the launch with `bytes`):
+//   [0)    Seg all[O * cap_o]; later the staged terms, double val[16][rows] | int idx[16][rows]
+//   [sel)  Seg sel[cap_sel]
+//   [dyn)  slopes [O][N][2] when staged; later s_ref[N] | l_ref[N] | ds_bounds[N][2]
+//   [ints) int ocount[64] | int word[4] | short slot_of[O * cap_o] | short pick[cap_sel]
+struct CorridorVjpLds { int rows; size_t sel, dyn, ints, bytes; };
+__host__ __device__ inline CorridorVjpLds corridor_vjp_lds(int N, int O, int cap_o, int cap_sel, int seg_stride, int staged) {
+  CorridorVjpLds l;
+  const size_t cap_all = (size_t)cap_o * O, seg_bytes = 104;   // sizeof(Seg)
+  l.rows = (cap_sel < seg_stride ? cap_sel : seg_stride) + 1;   // output segments, and one row for ref_end
+  const size_t terms = (size_t)kCorridorVjpTerms * l.rows * (sizeof(double) + sizeof(int));
+  l.sel = ((seg_bytes * cap_all > terms ? seg_bytes * cap_all : terms) + 15) & ~(size_t)15;
+  l.dyn = (l.sel + seg_bytes * cap_sel + 15) & ~(size_t)15;
+  const size_t table = staged ? (size_t)O * N * 2 : 0, refs = (size_t)N * 4;
+  l.ints = l.dyn + sizeof(double) * (table > refs ? table : refs);
+  l.bytes = l.ints + sizeof(int) * (64 + 4) + sizeof(short) * (cap_all + cap_sel);
+  return l;
+}
+__global__ void corridor_vjp_kernel(const CorridorVjpArgs a);
 // fixed_S = 0: bucket by segment count (ragged batches); > 0: uniform batch of fixed_S segments, bucket by hint class
 // candidates that cannot start: keys[b] = 0 and their records written here (btrapz_options.compact; btrapz_kernels.hip)
 __global__ void prestart_kernel(const KernelArgs a, int S_uniform, const int *seg_count, int *keys);

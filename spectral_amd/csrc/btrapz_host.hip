@@ -154,6 +154,7 @@ struct btrapz_ctx {
   Buf<int> d_retry{bufs};           // corridor stage: [0] count, [1..] candidates of the retry pass
   Buf<char> d_strips{bufs};         // btrapz_prism_corridor_batch_device's two-launch path: the strips
   Buf<char> d_corr_ws{bufs};        // corridor_serial_kernel's segment lists (horizons beyond the wave-wide kernels)
+  Buf<int> d_vjp_retry{bufs};       // the corridor stage's backward pass: [0] count, [1..] candidates of its retry pass
   Buf<int> d_long_list{bufs};       // ragged batches: the candidates of more than 64 segments, by count
   // The workspaces serve one launch sequence at a time.  Launches of one context issued on DIFFERENT streams are
   // ordered behind each other with this event (recorded after every sequence, waited for when the stream changes: ws_open).
@@ -1423,6 +1424,72 @@ BTRAPZ_EXPORT int btrapz_corridor_batch_device(btrapz_ctx *c, int variant, int B
   a.s_bounds = s_bounds; a.l_bounds = l_bounds; a.ds_bounds = ds_bounds; a.dl_bounds = dl_bounds_knots;
   a.s_ref = s_ref; a.l_ref = l_ref; a.seg = seg; a.seg_count = seg_count; a.ref_end = ref_end; a.dl10 = dl_bounds;
   return launch_corridor_stage(c, a, false, (hipStream_t)stream_);
+}
+
+// The backward pass of the stage (corridor_vjp.hip): zero the wanted outputs, then the forward's two passes -- lists sized
+// for the usual case, the candidates that overflow them again with the capacities the forward ends on.
+BTRAPZ_EXPORT int btrapz_corridor_batch_vjp_device(btrapz_ctx *c, int variant, int B, int N, int num_obs, double delta,
+                                                const double *s_bounds, const double *l_bounds, const double *ds_bounds,
+                                                const double *dl_bounds_knots, const double *s_ref, const double *l_ref,
+                                                int seg_stride, const double *seg_bar, const double *ref_end_bar,
+                                                const double *dl_bounds_bar, const btrapz_knot_grads *out, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (variant < 0 || variant > 1 || B < 1 || N < 3 || num_obs < 1 || !(delta > 0) || seg_stride < 1) {
+    c->err = "invalid argument: variant 0 or 1, B >= 1, N >= 3, num_obs >= 1, delta > 0 and seg_stride >= 1";
+    return BTRAPZ_EINVAL;
+  }
+  if (N > 512 || num_obs > 64 || seg_stride > BTRAPZ_MAX_SEGMENTS) {
+    c->err = "invalid argument: N > 512, num_obs > 64 or seg_stride > BTRAPZ_MAX_SEGMENTS -- beyond the wave-wide corridor kernels; "
+             "the serial one-lane-per-candidate path of the stage is not differentiated";
+    return BTRAPZ_EINVAL;
+  }
+  if (!s_bounds || !l_bounds || !ds_bounds || !dl_bounds_knots || !s_ref || !l_ref) {
+    c->err = "invalid argument: s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref and l_ref must be non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (!seg_bar && !ref_end_bar && !dl_bounds_bar) {
+    c->err = "invalid argument: seg_bar, ref_end_bar and dl_bounds_bar are all null";
+    return BTRAPZ_EINVAL;
+  }
+  if (!out || (!out->s_bounds && !out->l_bounds && !out->ds_bounds && !out->dl_bounds_knots && !out->s_ref && !out->l_ref)) {
+    c->err = "invalid argument: no output wanted (out, or every pointer of it, is null)";
+    return BTRAPZ_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  GROW(c, d_vjp_retry, sizeof(int) * ((size_t)B + 1));
+  HIPCHK(c, hipMemsetAsync(c->d_vjp_retry, 0, sizeof(int), stream));
+  const size_t pairs = sizeof(double) * 2 * (size_t)B * num_obs * N, knots = sizeof(double) * (size_t)B * N;
+  if (out->s_bounds) HIPCHK(c, hipMemsetAsync(out->s_bounds, 0, pairs, stream));
+  if (out->l_bounds) HIPCHK(c, hipMemsetAsync(out->l_bounds, 0, pairs, stream));
+  if (out->ds_bounds) HIPCHK(c, hipMemsetAsync(out->ds_bounds, 0, 2 * knots, stream));
+  if (out->dl_bounds_knots) HIPCHK(c, hipMemsetAsync(out->dl_bounds_knots, 0, 2 * knots, stream));
+  if (out->s_ref) HIPCHK(c, hipMemsetAsync(out->s_ref, 0, knots, stream));
+  if (out->l_ref) HIPCHK(c, hipMemsetAsync(out->l_ref, 0, knots, stream));
+  CorridorVjpArgs a;
+  memset(&a, 0, sizeof a);
+  a.B = B; a.N = N; a.num_obs = num_obs; a.variant = variant; a.seg_stride = seg_stride; a.delta = delta;
+  a.s_bounds = s_bounds; a.l_bounds = l_bounds; a.ds_bounds = ds_bounds; a.s_ref = s_ref; a.l_ref = l_ref;
+  a.seg_bar = seg_bar; a.ref_end_bar = ref_end_bar; a.dl10_bar = dl_bounds_bar; a.out = *out;
+  a.staged = sizeof(double) * 2 * (size_t)N * num_obs <= 24 * 1024 ? 1 : 0;
+  a.retry_count = c->d_vjp_retry; a.retry_list = c->d_vjp_retry + 1;
+  // (the forward's capacities: launch_corridor_stage)
+  const int cap_o_big = 160 / num_obs, cap_sel_big = 64;
+  int cap_o_small = (N - 1) / 10 + (N <= 128 ? 3 : 5), cap_sel_small = 2 * seg_stride < 16 ? 16 : 2 * seg_stride;
+  if (cap_o_small > cap_o_big) cap_o_small = cap_o_big;
+  if (cap_sel_small > cap_sel_big) cap_sel_small = cap_sel_big;
+  const bool two_pass = cap_o_small < cap_o_big || cap_sel_small < cap_sel_big;
+  a.pass = 0; a.cap_o = cap_o_small; a.cap_sel = cap_sel_small;
+  if (!two_pass) { a.retry_list = nullptr; a.retry_count = nullptr; }
+  hipLaunchKernelGGL(corridor_vjp_kernel, dim3(B), dim3(64), corridor_vjp_lds(N, num_obs, a.cap_o, a.cap_sel, seg_stride, a.staged).bytes, stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (two_pass) {
+    a.pass = 1; a.cap_o = cap_o_big; a.cap_sel = cap_sel_big;
+    const unsigned blocks = B < 1024 ? (unsigned)B : 1024u;
+    hipLaunchKernelGGL(corridor_vjp_kernel, dim3(blocks), dim3(64), corridor_vjp_lds(N, num_obs, a.cap_o, a.cap_sel, seg_stride, a.staged).bytes, stream, a);
+    HIPCHK(c, hipGetLastError());
+  }
+  return BTRAPZ_OK;
 }
 
 // Obstacle prisms -> strips -> corridors: btrapz_prism_bounds_device + btrapz_corridor_batch_device (num_obs = O) with

@@ -2,6 +2,7 @@
 #include "corridor.hpp"
 
 #include "corridor_core.h"
+#include "corridor_vjp_core.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -214,4 +215,75 @@ bool select_segments(int variant, double delta, const std::vector<std::vector<Se
   return true;
 }
 
+// ---- backward pass of the corridor stage, one candidate on the host (the twin of corridor_vjp_kernel) --------------------
+// The decisions are those of the device stage within the wave-wide kernels' limits: the serial statements of
+// corridor_core.h on lists of the capacities the forward's retry pass has, provenance noted in Seg::count.
+// Returns the forward's seg_count (0: nothing selected, -1: overflow or a segment with t <= 0).
+static int decide_with_provenance(int variant, int N, int O, double delta, const double *gs, const double *gl, const double *sref,
+                                  const double *lref, int seg_stride, std::vector<Seg> &sel) {
+  const int cap_o = VJP_MAX_ALL / O, cap_sel = VJP_MAX_SEL;
+  std::vector<Seg> list((size_t)cap_o);
+  sel.clear();
+  int carry = 0;
+  for (int o = 0; o < O; o++) {
+    const BoundsView sb{gs + (size_t)o * N * 2}, lb{gl + (size_t)o * N * 2};
+    const int n = extract_segments_core(variant, N, delta, sb, lb, SlopesOnTheFly{sb, delta}, list.data(), cap_o, ProvenanceNote{list.data()});
+    if (n < 0) return -1;
+    for (int j = 0; j < n; j++) {   // CollisionCheck's selection, solve_3d.cc:534-596
+      const Seg c = list[j];
+      int hits = 0;
+      for (int i = 0; i < N; i++) hits += knot_inside(c, sref[i], lref[i], (double)i, delta) ? 1 : 0;
+      for (int copies = selection_copies(selection_pushes(hits, carry), c); copies > 0; copies--) {
+        if ((int)sel.size() >= cap_sel) return -1;
+        Seg t = c; t.count = provenance_pack(o, c.count); sel.push_back(t);
+      }
+    }
+  }
+  if (sel.empty()) return 0;
+  const int S = order_segments_core(variant, delta, sel.data(), (int)sel.size());
+  if (S > seg_stride) return -1;
+  for (int k = 0; k < S; k++) if (!(sel[k].t > 0.0)) return -1;
+  return S;
+}
+
+namespace {
+struct HostSink {   // adds every term where it belongs, in the order it comes: segments ascending
+  double *g[VJP_GROUPS];
+  void add(int group, int /*p*/, int index, double value) { if (g[group] && index >= 0) g[group][index] += value; }
+};
+}  // namespace
+
 }  // namespace btrapz
+
+extern "C" __attribute__((visibility("default"))) int btrapz_corridor_vjp_host(
+    int variant, int N, int num_obs, double delta, const double *s_bounds, const double *l_bounds, const double *ds_bounds,
+    const double *dl_bounds_knots, const double *s_ref, const double *l_ref, int seg_stride, const double *seg_bar,
+    const double *ref_end_bar, const double *dl_bounds_bar, const btrapz_knot_grads *out, int *seg_count) {
+  using namespace btrapz;
+  if (variant < 0 || variant > 1 || N < 3 || N > VJP_MAX_KNOTS || num_obs < 1 || num_obs > VJP_MAX_OBS || !(delta > 0) || seg_stride < 1 ||
+      seg_stride > BTRAPZ_MAX_SEGMENTS || !s_bounds || !l_bounds || !ds_bounds || !dl_bounds_knots || !s_ref || !l_ref ||
+      (!seg_bar && !ref_end_bar && !dl_bounds_bar) || !out ||
+      (!out->s_bounds && !out->l_bounds && !out->ds_bounds && !out->dl_bounds_knots && !out->s_ref && !out->l_ref))
+    return BTRAPZ_EINVAL;
+  const size_t n_pairs = (size_t)num_obs * N * 2;
+  auto zero = [](double *p, size_t n) { if (p) for (size_t i = 0; i < n; i++) p[i] = 0.0; };
+  zero(out->s_bounds, n_pairs); zero(out->l_bounds, n_pairs); zero(out->ds_bounds, (size_t)N * 2);
+  zero(out->dl_bounds_knots, (size_t)N * 2); zero(out->s_ref, (size_t)N); zero(out->l_ref, (size_t)N);
+  std::vector<Seg> sel;
+  const int S = decide_with_provenance(variant, N, num_obs, delta, s_bounds, l_bounds, s_ref, l_ref, seg_stride, sel);
+  if (seg_count) *seg_count = S;
+  if (S < 1) return BTRAPZ_OK;
+  HostSink sink{{out->s_bounds, out->l_bounds, out->ds_bounds, out->s_ref, out->l_ref}};
+  for (int k = 0; k < S; k++)
+    segment_adjoint(variant, N, delta, k, sel[k], ds_bounds, seg_bar ? seg_bar + k : nullptr, (size_t)seg_stride, sink);
+  if (ref_end_bar) {
+    if (out->s_ref) out->s_ref[N - 1] += ref_end_bar[0];
+    if (out->l_ref) out->l_ref[N - 1] += ref_end_bar[1];
+  }
+  if (dl_bounds_bar && out->dl_bounds_knots)
+    for (int j = 0; j < 10; j++) {
+      const int i = j >> 1, ii = i > N - 1 ? N - 1 : i;
+      out->dl_bounds_knots[2 * ii + (j & 1)] += dl_bounds_bar[j];
+    }
+  return BTRAPZ_OK;
+}

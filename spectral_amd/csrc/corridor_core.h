@@ -72,8 +72,12 @@ struct SlopeTable {  // interleaved (down, up) pairs, entry i at p[2 i]
 // ---- CorridorGeneration + CorridorSplit for one obstacle.  Returns the number of segments written,
 // or -1 when `cap` is too small.
 // (SB, LB: anything with lo(i) / hi(i) -- BoundsView, or the strips of the fused prism + corridor kernel)
-template <class SB, class LB, class Slopes>
-BTRAPZ_HD int extract_segments_core(int variant, int N, double delta, SB sb, LB lb, Slopes sk, Seg *v, int cap) {
+// note(slot, i0, h): told, for every segment written, the knot i0 at which its base segment opened and the number h of
+// one-second pieces in front of it -- what the stage's backward pass (corridor_vjp_core.h) needs to know and cannot read
+// off the segment.  The default does nothing and leaves no code behind.
+struct NoSegmentNote { BTRAPZ_HD void operator()(int, int, int) const {} };
+template <class SB, class LB, class Slopes, class Note = NoSegmentNote>
+BTRAPZ_HD int extract_segments_core(int variant, int N, double delta, SB sb, LB lb, Slopes sk, Seg *v, int cap, Note note = Note()) {
   if (cap < 1 || N < 3) return -1;
   int n = 0;
   {
@@ -129,6 +133,8 @@ BTRAPZ_HD int extract_segments_core(int variant, int N, double delta, SB sb, LB 
     { double t = rest.t; while (t > 1) { t = t - 1; h++; } }
     pos -= h + 1;
     int w = pos;
+    const int opened_at = rest.beg_t;
+    int pieces = 0;
     while (rest.t > 1) {
       rest.t = rest.t - 1;
       Seg head = seg_default();
@@ -146,8 +152,10 @@ BTRAPZ_HD int extract_segments_core(int variant, int N, double delta, SB sb, LB 
       rest.down_bias = head.down_bias + 1.0 * head.down_skew;
       rest.upp_bias = head.upp_bias + 1.0 * head.upp_skew;
       v[w++] = head;
+      note(w - 1, opened_at, pieces++);
     }
     v[w] = rest;
+    note(w, opened_at, pieces);
   }
   return total;
 }
@@ -210,7 +218,9 @@ BTRAPZ_HD int selection_copies(int pushes, const Seg &c) { return selection_copi
 // De-dup (keep first), then ordering and time-overlap resolution: solve_3d.cc:617-703 (trapezoid),
 // cuboid_3d.cc:538-567 (cuboid: no sort, no reorder, every later twin, a third of the span).  Separate steps so that
 // the device can run all but the overlap walk across the lanes (corridor_kernels.hip).
-BTRAPZ_HD int dedup_segments_core(Seg *v, int n) {
+// (S: Seg, or a type derived from it that copies itself another way -- corridor_vjp.hip)
+template <class S>
+BTRAPZ_HD int dedup_segments_core(S *v, int n) {
   for (int i = 0; i + 1 < n; i++)
     for (int j = i + 1; j < n;) {
       if (same_segment(v[i], v[j])) { for (int m = j; m + 1 < n; m++) v[m] = v[m + 1]; n--; } else j++;
@@ -342,35 +352,42 @@ BTRAPZ_HD bool std_sort_core(T *v, int n, Key key, int *frames) {
   return heap_sorted;
 }
 // Returns whether the heap-sort fallback ran (a fact about the input the tests ask for).
-BTRAPZ_HD bool sort_segments_core(Seg *v, int n) {
+// (S: Seg, or a type derived from it; frames: std_sort_core's, from the caller where a local array would cost a stack)
+template <class S>
+BTRAPZ_HD bool sort_segments_core(S *v, int n, int *frames) {
   if (n <= STD_SORT_THRESHOLD) {  // the guarded insertion pass alone: a stable insertion sort by beg_t
     for (int i = 1; i < n; i++) {
-      const Seg x = v[i];
+      const S x = v[i];
       int j = i - 1;
       while (j >= 0 && x.beg_t < v[j].beg_t) { v[j + 1] = v[j]; j--; }
       v[j + 1] = x;
     }
     return false;
   }
-  int frames[3 * 2 * 31];
   return std_sort_core(v, n, SegBegT(), frames);
+}
+BTRAPZ_HD bool sort_segments_core(Seg *v, int n) {
+  int frames[3 * 2 * 31];
+  return sort_segments_core(v, n, frames);
 }
 // Trapezoid variant, first half: pull a segment that continues segment i's lane next to it (solve_3d.cc:640-666).
 // Only beg_l, beg_t and end_t are compared; the device runs the k search across the lanes (corridor_kernels.hip).
-BTRAPZ_HD void reorder_segments_core(Seg *v, int n) {
+template <class S>
+BTRAPZ_HD void reorder_segments_core(S *v, int n) {
   for (int i = 0; i + 1 < n; i++)
     for (int j = i + 1; j < n; j++) {
       if (v[i].beg_l == v[j].beg_l && j - i == 1) break;
       for (int k = j + 1; k < n; k++)
-        if (v[i].beg_l == v[k].beg_l && v[i].end_t == v[k].beg_t) { const Seg x = v[j]; v[j] = v[k]; v[k] = x; break; }
+        if (v[i].beg_l == v[k].beg_l && v[i].end_t == v[k].beg_t) { const S x = v[j]; v[j] = v[k]; v[k] = x; break; }
     }
 }
 // Time overlaps: between neighbours (trapezoid, solve_3d.cc:678-703: its inner loop breaks after j = i + 1) or between every pair of twins (cuboid).
 // Each step sees the spans the previous one left, so this stays a serial walk on the device too.
-BTRAPZ_HD void overlap_segments_core(int variant, double delta, Seg *v, int n) {
+template <class S>
+BTRAPZ_HD void overlap_segments_core(int variant, double delta, S *v, int n) {
   if (variant == 0) {
     for (int i = 0; i + 1 < n; i++) {
-      Seg &a = v[i], &b = v[i + 1];
+      S &a = v[i], &b = v[i + 1];
       if (a.beg_t == b.beg_t && a.end_t == b.end_t) {
         const int half = (a.end_t - a.beg_t) / 2;
         a.end_t -= half; a.t = (a.end_t - a.beg_t) * delta;
@@ -391,7 +408,8 @@ BTRAPZ_HD void overlap_segments_core(int variant, double delta, Seg *v, int n) {
         }
   }
 }
-BTRAPZ_HD void resolve_segments_core(int variant, double delta, Seg *v, int n) {
+template <class S>
+BTRAPZ_HD void resolve_segments_core(int variant, double delta, S *v, int n) {
   if (variant == 0) reorder_segments_core(v, n);
   overlap_segments_core(variant, delta, v, n);
 }

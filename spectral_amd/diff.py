@@ -359,3 +359,36 @@ def eval_states_jvp(solver, dctrl, seg, times, seg_count=None):
     with torch.no_grad():
         x = eval_states(dctrl.reshape(T * B, -1), seg.repeat(1, T, 1).contiguous(), times.repeat(T, 1).contiguous(), solver, seg_count=cnt)
     return x.reshape(T, B, 2, times.shape[1], 3)
+
+
+class _Corridor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, solver, variant, delta, seg_stride):
+        d = solver.device
+        ins = [_f64(t.detach()).to(d) for t in (s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref)]
+        B, N = ins[0].shape[0], ins[0].shape[2]
+        init = torch.zeros((B, 6), dtype=torch.float64, device=d)   # (the stage does not read it)
+        rec = solver.corridor_batch_tensors(variant, N, delta, *ins, init, seg_stride=seg_stride)
+        ctx.solver, ctx.ins, ctx.variant, ctx.delta, ctx.seg_stride = solver, ins, variant, delta, seg_stride
+        ctx.mark_non_differentiable(rec["seg_count"])
+        return rec["seg"], rec["seg_count"], rec["ref_end"], rec["dl_bounds"]
+
+    @staticmethod
+    def backward(ctx, seg_bar, _count_bar, ref_end_bar, dl_bounds_bar):
+        names = ("s_bounds", "l_bounds", "ds_bounds", "dl_bounds_knots", "s_ref", "l_ref")
+        want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:6]) if need)
+        if not want or (seg_bar is None and ref_end_bar is None and dl_bounds_bar is None):
+            return (None,) * 10
+        g = ctx.solver.corridor_batch_vjp(ctx.ins, ctx.variant, seg_bar, ref_end_bar, dl_bounds_bar, want=want, delta=ctx.delta,
+                                          seg_stride=ctx.seg_stride)
+        return tuple(g.get(n) for n in names) + (None, None, None, None)
+
+
+def corridor(solver, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, *, variant=0, delta=0.1, seg_stride=16):
+    """The device corridor stage as a differentiable layer (btrapz_corridor_batch_device; backward: one
+    btrapz_corridor_batch_vjp_device launch).  s_bounds, l_bounds [B, O, N, 2]; ds_bounds, dl_bounds_knots [B, N, 2]; s_ref,
+    l_ref [B, N].  Returns (seg [NUM_SEG_FIELDS, B, seg_stride], seg_count [B], ref_end [B, 2], dl_bounds [B, 10]) -- what
+    diff.solve(...) takes, with seg_count for the ragged batch; seg_count is not differentiable.  The stage's discrete
+    decisions are frozen: the gradient is that of the piecewise linear map around the inputs (include/btrapz_hip.h lists
+    the rules); candidates without a corridor (seg_count 0 or -1) get zeros.  Up to 512 knots and 64 obstacles."""
+    return _Corridor.apply(s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, solver, int(variant), float(delta), int(seg_stride))

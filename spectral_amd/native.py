@@ -69,6 +69,16 @@ class CTangents(C.Structure):
 MAX_TANGENTS = 32   # BTRAPZ_MAX_TANGENTS
 
 
+class CKnotGrads(C.Structure):
+    """btrapz_knot_grads (include/btrapz_hip.h): pointers of the gradient arrays of btrapz_corridor_batch_vjp_device
+    (device) / btrapz_corridor_vjp_host (host)."""
+    _fields_ = [("s_bounds", C.c_void_p), ("l_bounds", C.c_void_p), ("ds_bounds", C.c_void_p),
+                ("dl_bounds_knots", C.c_void_p), ("s_ref", C.c_void_p), ("l_ref", C.c_void_p)]
+
+
+KNOT_GRADS = ("s_bounds", "l_bounds", "ds_bounds", "dl_bounds_knots", "s_ref", "l_ref")
+
+
 class CWarm(C.Structure):
     """btrapz_warm (include/btrapz_hip.h): optional warm start of a solve."""
     _fields_ = [("x0", C.c_void_p), ("lam0", C.c_void_p), ("lam_out", C.c_void_p),
@@ -135,7 +145,7 @@ class CRoad(C.Structure):
 EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "btrapz_destroy", "btrapz_last_error",
            "btrapz_device_count", "btrapz_solve_batch_device", "btrapz_argmin_device",
            "btrapz_sample_device", "btrapz_solve_batch_host", "btrapz_solve_ragged_device",
-           "btrapz_corridor_batch_device", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
+           "btrapz_corridor_batch_device", "btrapz_corridor_batch_vjp_device", "btrapz_corridor_vjp_host", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
            "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_solve_jvp_device", "btrapz_traj_cost_device", "btrapz_traj_cost_vjp_device",
            "btrapz_eval_states_device", "btrapz_sample_vjp_device", "btrapz_eval_states_vjp_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
            "btrapz_prism_corridor_batch_device",
@@ -230,6 +240,10 @@ def lib():
                                                  dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
         l.btrapz_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                                    dp, dp, dp, dp, dp, dp, C.c_int, dp, ip, dp, dp, vp]
+        l.btrapz_corridor_batch_vjp_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                       dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp, C.POINTER(CKnotGrads), vp]
+        l.btrapz_corridor_vjp_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, dp, dp, dp, dp, dp, dp, C.c_int,
+                                               dp, dp, dp, C.POINTER(CKnotGrads), C.POINTER(C.c_int)]
         l.btrapz_sample_ragged_device.argtypes = [vp, C.c_int, C.c_int, ip, C.c_double, dp, dp, dp, C.c_int, llp,
                                                   C.c_int, dp, ip, vp]
         l.btrapz_solve_warm_device.argtypes = [vp, C.POINTER(CShared), C.POINTER(COptions), C.POINTER(CWarm), C.c_int,
@@ -602,6 +616,20 @@ class Context:
                                                        ptr(seg), ptr(seg_count), ptr(ref_end), ptr(dl_bounds),
                                                        C.c_void_p(stream or 0)), "btrapz_corridor_batch_device")
 
+    def corridor_batch_vjp_device(self, variant, B, N, num_obs, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots,
+                                  s_ref, l_ref, seg_stride, seg_bar, ref_end_bar, dl_bounds_bar, grads, stream=None):
+        """btrapz_corridor_batch_vjp_device: grads = dict name -> device tensor (KNOT_GRADS; missing or None: not wanted),
+        overwritten; the cotangents may be None."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        raw = lambda t: t.data_ptr() if t is not None else None
+        g = CKnotGrads(*[raw(grads.get(k)) for k in KNOT_GRADS]) if grads is not None else None
+        self._check(lib().btrapz_corridor_batch_vjp_device(self._h, int(variant), int(B), int(N), int(num_obs), float(delta),
+                                                           ptr(s_bounds), ptr(l_bounds), ptr(ds_bounds), ptr(dl_bounds_knots),
+                                                           ptr(s_ref), ptr(l_ref), int(seg_stride), ptr(seg_bar),
+                                                           ptr(ref_end_bar), ptr(dl_bounds_bar),
+                                                           C.byref(g) if g is not None else None, C.c_void_p(stream or 0)),
+                    "btrapz_corridor_batch_vjp_device")
+
     def prism_bounds_device(self, B, P, N, road, prisms, O, s_bounds, l_bounds, n_strips, stream=None):
         ptr = lambda t: C.c_void_p(t.data_ptr())
         self._check(lib().btrapz_prism_bounds_device(self._h, B, P, N, C.byref(road), ptr(prisms), O, ptr(s_bounds),
@@ -692,6 +720,30 @@ def find_traj_mem(variant, params, kb, b=0, cap=None):
     """btrapz_find_traj_mem(): find_traj on candidate b of a spectral_amd.knots.KnotBatch (arrays in, arrays out).
     Returns (cost, traj [7][n] rows t s l ds dl dds ddl, ctrl [12 S]); cost == 1e11 on failure (traj, ctrl None)."""
     return TrajCall(variant, params, kb, b, cap)()
+
+
+def corridor_vjp_host(variant, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, seg_stride, seg_bar=None,
+                      ref_end_bar=None, dl_bounds_bar=None, want=KNOT_GRADS):
+    """btrapz_corridor_vjp_host(): the backward pass of the corridor stage for ONE candidate on the host (no GPU).
+    s_bounds, l_bounds [num_obs, N, 2]; ds_bounds, dl_bounds_knots [N, 2]; s_ref, l_ref [N]; seg_bar
+    [NUM_SEG_FIELDS, seg_stride], ref_end_bar [2], dl_bounds_bar [10] (any may be None).  Returns (dict of the wanted
+    gradient arrays, the forward's seg_count)."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    sb, lb, ds, dl, sr, lr = (f(a) for a in (s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref))
+    num_obs, N = (sb.shape[0], sb.shape[1]) if sb is not None else (0, 0)
+    bars = [f(seg_bar), f(ref_end_bar), f(dl_bounds_bar)]
+    if bars[0] is not None:
+        assert bars[0].shape == (L.NUM_SEG_FIELDS, seg_stride)
+    shapes = dict(s_bounds=(num_obs, N, 2), l_bounds=(num_obs, N, 2), ds_bounds=(N, 2), dl_bounds_knots=(N, 2), s_ref=(N,), l_ref=(N,))
+    out = {k: np.full(shapes[k], np.nan) for k in want}
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    g = CKnotGrads(*[out[k].ctypes.data if k in out else None for k in KNOT_GRADS])
+    count = C.c_int(-2)
+    rc = lib().btrapz_corridor_vjp_host(int(variant), int(N), int(num_obs), float(delta), p(sb), p(lb), p(ds), p(dl), p(sr), p(lr),
+                                        int(seg_stride), p(bars[0]), p(bars[1]), p(bars[2]), C.byref(g), C.byref(count))
+    if rc != 0:
+        raise BtrapzError("btrapz_corridor_vjp_host -> %d (invalid argument)" % rc)
+    return out, count.value
 
 
 def corridor_from_file(variant, input_path, cap=256):

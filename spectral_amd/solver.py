@@ -116,6 +116,42 @@ class BatchSolver:
         rec["_inputs"] = ins  # keep the knot arrays alive until the launch has run
         return rec
 
+    def corridor_batch_vjp(self, kb_or_tensors, variant, seg_bar, ref_end_bar=None, dl_bounds_bar=None,
+                           want=("s_bounds", "l_bounds", "ds_bounds", "dl_bounds_knots", "s_ref", "l_ref"), delta=None,
+                           seg_stride=None):
+        """Gradients of the device corridor stage w.r.t. its per-knot inputs (btrapz_corridor_batch_vjp_device).
+        kb_or_tensors: a spectral_amd.knots.KnotBatch, or the six arrays (s_bounds, l_bounds [B, O, N, 2]; ds_bounds,
+        dl_bounds_knots [B, N, 2]; s_ref, l_ref [B, N]) as tensors with `delta` given.  seg_bar [NUM_SEG_FIELDS, B,
+        seg_stride], ref_end_bar [B, 2], dl_bounds_bar [B, 10]: cotangents of the stage's outputs (any may be None, not
+        all).  seg_stride: the forward call's (a corridor of more segments has seg_count -1 there and zeros here); it may be
+        left out with a seg_bar, whose last extent it is, and is required without one.  Returns a dict of the arrays named
+        in `want`, shaped like the inputs."""
+        d = self.device
+        if hasattr(kb_or_tensors, "s_bounds"):
+            kb = kb_or_tensors
+            f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(d)
+            ins = [f(kb.s_bounds), f(kb.l_bounds), f(kb.ds_bounds), f(kb.dl_bounds), f(kb.s_ref), f(kb.l_ref)]
+            delta = kb.delta if delta is None else delta
+        else:
+            ins = [t.detach().to(d, dtype=torch.float64).contiguous() for t in kb_or_tensors]
+            if delta is None:
+                raise ValueError("delta is needed with tensors")
+        B, O, N = ins[0].shape[0], ins[0].shape[1], ins[0].shape[2]
+        c = lambda t: None if t is None else t.detach().to(d, dtype=torch.float64).contiguous()
+        seg_bar, ref_end_bar, dl_bounds_bar = c(seg_bar), c(ref_end_bar), c(dl_bounds_bar)
+        if seg_bar is None and seg_stride is None:
+            raise ValueError("seg_stride is needed without a seg_bar")
+        if seg_bar is not None and seg_stride is not None and int(seg_stride) != seg_bar.shape[2]:
+            raise ValueError("seg_stride %d is not seg_bar's, %d" % (seg_stride, seg_bar.shape[2]))
+        seg_stride = seg_bar.shape[2] if seg_bar is not None else int(seg_stride)
+        like = dict(s_bounds=ins[0], l_bounds=ins[1], ds_bounds=ins[2], dl_bounds_knots=ins[3], s_ref=ins[4], l_ref=ins[5])
+        grads = {k: torch.empty_like(like[k]) for k in want}
+        stream = torch.cuda.current_stream(d).cuda_stream
+        self.ctx.corridor_batch_vjp_device(variant, B, N, O, delta, *ins, seg_stride, seg_bar, ref_end_bar, dl_bounds_bar,
+                                           grads, stream=stream)
+        grads["_inputs"] = (ins, seg_bar, ref_end_bar, dl_bounds_bar)   # alive until the launch has run
+        return grads
+
     def prism_bounds(self, prisms, N, O, road=None):
         """Obstacle prisms [B, P, 8] (s0, l0, t0, vel_s, vel_l, T, active, -) -> per-knot bounds of the lateral strips
         (btrapz_prism_bounds_device): s_bounds, l_bounds [B, O, N, 2] and n_strips [B], on the device."""
