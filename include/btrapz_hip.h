@@ -502,6 +502,40 @@ typedef struct btrapz_road {
 int btrapz_prism_bounds_device(btrapz_ctx *ctx, int B, int P, int N, const btrapz_road *road, const double *prisms,
                                int O, double *s_bounds, double *l_bounds, int *n_strips, void *stream);
 
+/* ---- gradients of the prism stage w.r.t. the obstacle prisms --------------------------------------------------------
+ * Cotangents of s_bounds / l_bounds [B][O][N][2] in, prisms_bar [B][P][8] out: s0, l0, t0, vel_s, vel_l, T, then two zeros
+ * (`active` and `reserved` are not differentiated).  The stage's discrete decisions are FROZEN and made again here from
+ * `prisms` and `road` with the forward's own statements and rounded values (nothing is taken from a forward call): the
+ * active flags, ahead = (t0 == 0), the branch vel_l >= 0, whether knot i lies in a car's window, the sorted distinct edges
+ * and the candidate that supplied each, the cars that cover a strip, the car that wins each max / min.  With them frozen
+ * the stage is a sparse map, at most bilinear in every parameter:
+ *   lateral extent: vel_l >= 0: l_min = l0 - w_safe, l_max = l0 + vel_l T + w_safe; vel_l < 0: l_min = l0 + vel_l T - w_safe,
+ *       l_max = l0 + w_safe.  The `l0 + vel_l T` end has derivatives 1, T, vel_l w.r.t. l0, vel_l, T; the other end 1 w.r.t. l0.
+ *   edges: edge[j] is the j-th distinct value among the candidates l_min of cars 0..P-1, l_max of cars 0..P-1, the road's two
+ *       edges; the LOWEST-INDEX candidate with that value supplied it and receives its gradient, a road edge passes it to
+ *       nobody.  l_bounds[j][i] = (edge[j], edge[j+1]) at every knot: edge_bar[j] = sum_i l_bar[j][i][0] + sum_i l_bar[j-1][i][1].
+ *   faces: the forward evaluates round2(c i / rate - c t0 + y1), c = (y2 - y1) / ((t0 + T) - t0): in exact arithmetic the line
+ *       s0 -+ l_safe + vel_s (i / rate - t0).  THE TWO-DECIMAL ROUNDING IS DIFFERENTIATED AS THE IDENTITY (straight-through):
+ *       taken literally its derivative is 0 almost everywhere.  A face value at knot i has derivatives 1, (i / rate - t0),
+ *       -vel_s, 0 w.r.t. s0, vel_s, t0, T; the role of t0 and T in the window and of t0 in `ahead` are decisions.
+ *   strip bounds: the first covering car's (c_lo, c_hi) replace the road's limits, later cars replace only when strictly
+ *       tighter (on a tie the earlier car keeps it).  s_bar[j][i][0] goes to the car whose value is the lower bound, if that
+ *       value is its face (inside the window and not ahead); if it is road.s_lo, to nobody.  [..][1] the same with ahead, s_hi.
+ * Defined cases: an inactive slot gets 0; cotangents of padding strips (j >= n_strips) are ignored; a scene with more strips
+ * than O (the forward's n_strips = -1) gets 0 everywhere; a NULL cotangent array is zero; prisms_bar is OVERWRITTEN, never
+ * accumulated into; sums are taken in a fixed order without atomics -- per lane of a 64-lane wavefront over strips and knots
+ * i = lane, lane + 64, .. ascending, then a butterfly (xor 32, 16, .. 1) across the lanes -- so the same inputs give the same
+ * bits on every run, and the host call below gives the device call's bits.
+ * The device call is asynchronous and stream-ordered (one launch, no host round trip); limits as the forward: P <= 16.
+ * Refused with BTRAPZ_EINVAL (btrapz_last_error says why on the device call): prisms, road or prisms_bar NULL; both
+ * cotangents NULL; B, P, N or O < 1; P > 16; knots_per_second not > 0. */
+int btrapz_prism_bounds_vjp_device(btrapz_ctx *ctx, int B, int P, int N, const btrapz_road *road, const double *prisms,
+                                   int O, const double *s_bounds_bar, const double *l_bounds_bar, double *prisms_bar,
+                                   void *stream);
+/* The same on the host (no GPU, no context): every pointer a host pointer. */
+int btrapz_prism_bounds_vjp_host(int B, int P, int N, const btrapz_road *road, const double *prisms, int O,
+                                 const double *s_bounds_bar, const double *l_bounds_bar, double *prisms_bar);
+
 /* Obstacle prisms -> corridors in ONE launch: btrapz_prism_bounds_device followed by btrapz_corridor_batch_device with
  * num_obs = O, with the strips evaluated inside the corridor kernel where it reads them instead of written to memory
  * and read back (2 x 32 O N bytes per scene less traffic, one launch less).  Same outputs, bit for bit

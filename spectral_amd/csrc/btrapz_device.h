@@ -301,6 +301,8 @@ __global__ void single_candidate_warm_kernel(const KernelArgs a, const double *_
 
 // library-internal: the HIP device a context lives on
 int btrapz_ctx_device(const btrapz_ctx *ctx);
+// library-internal: what btrapz_last_error returns next, for the entry points defined outside btrapz_host.hip
+void btrapz_ctx_set_error(btrapz_ctx *ctx, const char *what);
 // library-internal: find_traj's single-candidate path.  One launch; in and out may be host memory
 // mapped into the device.  in: seg[17 S] init[6] ref_end[2] dl[10] mqm[168]; out: cost, status|iters, np, ctrl[12 S],
 // traj[6 max_points].  The M'QM table comes from the caller (btrapz_mqm_table_host).

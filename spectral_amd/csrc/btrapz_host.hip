@@ -213,6 +213,7 @@ static int ws_close(btrapz_ctx *c, hipStream_t stream) {
 }
 
 int btrapz_ctx_device(const btrapz_ctx *c) { return c ? c->device : 0; }
+void btrapz_ctx_set_error(btrapz_ctx *c, const char *what) { if (c) c->err = what; }
 
 BTRAPZ_EXPORT int btrapz_device_count(void) {
   int n = 0;

@@ -392,3 +392,31 @@ def corridor(solver, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_re
     decisions are frozen: the gradient is that of the piecewise linear map around the inputs (include/btrapz_hip.h lists
     the rules); candidates without a corridor (seg_count 0 or -1) get zeros.  Up to 512 knots and 64 obstacles."""
     return _Corridor.apply(s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, solver, int(variant), float(delta), int(seg_stride))
+
+
+class _PrismBounds(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prisms, solver, N, O, road):
+        p = _f64(prisms.detach()).to(solver.device)
+        sb, lb, n = solver.prism_bounds(p, N, O, road=road)
+        ctx.solver, ctx.prisms, ctx.N, ctx.O, ctx.road = solver, p, N, O, road
+        ctx.shape, ctx.device_in = prisms.shape, prisms.device
+        ctx.mark_non_differentiable(n)
+        return sb, lb, n
+
+    @staticmethod
+    def backward(ctx, s_bar, l_bar, _n_bar):
+        if not ctx.needs_input_grad[0] or (s_bar is None and l_bar is None):
+            return (None,) * 5
+        g = ctx.solver.prism_bounds_vjp(ctx.prisms, ctx.N, ctx.O, s_bar, l_bar, road=ctx.road)
+        return (g.reshape(ctx.shape).to(ctx.device_in), None, None, None, None)
+
+
+def prism_bounds(solver, prisms, N, O, road=None):
+    """The prism stage as a differentiable layer (btrapz_prism_bounds_device; backward: one
+    btrapz_prism_bounds_vjp_device launch).  prisms [B, P, 8]: s0, l0, t0, vel_s, vel_l, T, active, reserved.  Returns
+    (s_bounds, l_bounds [B, O, N, 2], n_strips [B]) -- what diff.corridor(...) takes as its first two arguments; n_strips is
+    not differentiable.  The stage's discrete decisions are frozen and the two-decimal rounding of the faces is
+    differentiated as the identity (include/btrapz_hip.h lists the rules); `active` and `reserved` get 0, and so does every
+    entry of a scene with more than O strips."""
+    return _PrismBounds.apply(prisms, solver, int(N), int(O), road)

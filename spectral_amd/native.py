@@ -148,7 +148,7 @@ EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "bt
            "btrapz_corridor_batch_device", "btrapz_corridor_batch_vjp_device", "btrapz_corridor_vjp_host", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
            "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_solve_jvp_device", "btrapz_traj_cost_device", "btrapz_traj_cost_vjp_device",
            "btrapz_eval_states_device", "btrapz_sample_vjp_device", "btrapz_eval_states_vjp_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
-           "btrapz_prism_corridor_batch_device",
+           "btrapz_prism_corridor_batch_device", "btrapz_prism_bounds_vjp_device", "btrapz_prism_bounds_vjp_host",
            "btrapz_find_traj_last_iterations", "btrapz_argmin_pairs_device", "btrapz_options_init",
            "btrapz_rescue_violations_device", "btrapz_find_traj_last_status", "btrapz_debug_mqm_tables",
            "btrapz_debug_axis_records", "btrapz_debug_resume_keys", "btrapz_debug_parse_double", "btrapz_debug_format_fixed",
@@ -262,6 +262,8 @@ def lib():
         l.btrapz_sample_vjp_device.argtypes = [vp, C.c_int, C.c_int, ip, C.c_double, dp, C.c_int, llp, C.c_int, dp, dp, dp, vp]
         l.btrapz_eval_states_vjp_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, dp, dp, vp]
         l.btrapz_prism_bounds_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, ip, vp]
+        l.btrapz_prism_bounds_vjp_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, dp, vp]
+        l.btrapz_prism_bounds_vjp_host.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, dp]
         l.btrapz_prism_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int,
                                                          C.c_double, dp, dp, dp, dp, C.c_int, dp, ip, dp, dp, ip, vp]
         l.btrapz_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int]
@@ -636,6 +638,14 @@ class Context:
                                                      ptr(l_bounds), ptr(n_strips), C.c_void_p(stream or 0)),
                     "btrapz_prism_bounds_device")
 
+    def prism_bounds_vjp_device(self, B, P, N, road, prisms, O, s_bounds_bar, l_bounds_bar, prisms_bar, stream=None):
+        """btrapz_prism_bounds_vjp_device: prisms_bar [B, P, 8] is overwritten; either cotangent may be None (zero)."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(lib().btrapz_prism_bounds_vjp_device(self._h, int(B), int(P), int(N), C.byref(road) if road is not None else None,
+                                                         ptr(prisms), int(O), ptr(s_bounds_bar), ptr(l_bounds_bar),
+                                                         ptr(prisms_bar), C.c_void_p(stream or 0)),
+                    "btrapz_prism_bounds_vjp_device")
+
     def prism_corridor_batch_device(self, variant, B, P, N, road, prisms, O, delta, ds_bounds, dl_bounds_knots, s_ref, l_ref,
                                     seg_stride, seg, seg_count, ref_end, dl_bounds, n_strips=None, stream=None):
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
@@ -720,6 +730,26 @@ def find_traj_mem(variant, params, kb, b=0, cap=None):
     """btrapz_find_traj_mem(): find_traj on candidate b of a spectral_amd.knots.KnotBatch (arrays in, arrays out).
     Returns (cost, traj [7][n] rows t s l ds dl dds ddl, ctrl [12 S]); cost == 1e11 on failure (traj, ctrl None)."""
     return TrajCall(variant, params, kb, b, cap)()
+
+
+def prism_bounds_vjp_host(prisms, N, O, s_bounds_bar=None, l_bounds_bar=None, road=None):
+    """btrapz_prism_bounds_vjp_host(): the backward pass of the prism stage on the host (no GPU).  prisms [B, P, 8];
+    s_bounds_bar, l_bounds_bar [B, O, N, 2] (either may be None: zero).  Returns prisms_bar [B, P, 8]."""
+    prisms = np.ascontiguousarray(prisms, dtype=np.float64)
+    if prisms.ndim != 3 or prisms.shape[2] != 8:
+        raise ValueError("prisms must be [B, P, 8]")
+    B, P = prisms.shape[0], prisms.shape[1]
+    bars = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (s_bounds_bar, l_bounds_bar)]
+    for a in bars:
+        if a is not None and a.shape != (B, int(O), int(N), 2):
+            raise ValueError("a cotangent must be [B, O, N, 2]")
+    out = np.full((B, P, 8), np.nan)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    road = CRoad.reference() if road is None else road
+    rc = lib().btrapz_prism_bounds_vjp_host(B, P, int(N), C.byref(road), p(prisms), int(O), p(bars[0]), p(bars[1]), p(out))
+    if rc != 0:
+        raise BtrapzError("btrapz_prism_bounds_vjp_host -> %d (invalid argument)" % rc)
+    return out
 
 
 def corridor_vjp_host(variant, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, seg_stride, seg_bar=None,

@@ -165,6 +165,25 @@ class BatchSolver:
         self.ctx.prism_bounds_device(B, P, N, road or CRoad.reference(), prisms, O, sb, lb, n, stream=stream)
         return sb, lb, n
 
+    def prism_bounds_vjp(self, prisms, N, O, s_bounds_bar, l_bounds_bar, road=None):
+        """Gradients of prism_bounds w.r.t. the prisms (btrapz_prism_bounds_vjp_device, one launch): cotangents
+        s_bounds_bar, l_bounds_bar [B, O, N, 2] (either may be None, not both) -> prisms_bar [B, P, 8]: s0, l0, t0, vel_s,
+        vel_l, T, then two zeros.  The stage's decisions are frozen and the two-decimal rounding of the faces counts as the
+        identity (include/btrapz_hip.h lists the rules); a scene with more than O strips gets zeros."""
+        from .native import CRoad
+        d = self.device
+        prisms = prisms.detach().to(d, dtype=torch.float64).contiguous()
+        B, P = prisms.shape[0], prisms.shape[1]
+        c = lambda t: None if t is None else t.detach().to(d, dtype=torch.float64).contiguous()
+        sbar, lbar = c(s_bounds_bar), c(l_bounds_bar)
+        for t in (sbar, lbar):
+            if t is not None and tuple(t.shape) != (B, int(O), int(N), 2):
+                raise ValueError("a cotangent must be [B, O, N, 2] = %s, not %s" % ((B, O, N, 2), tuple(t.shape)))
+        out = torch.empty((B, P, 8), dtype=torch.float64, device=d)
+        stream = torch.cuda.current_stream(d).cuda_stream
+        self.ctx.prism_bounds_vjp_device(B, P, N, road or CRoad.reference(), prisms, O, sbar, lbar, out, stream=stream)
+        return out
+
     def corridor_batch_tensors(self, variant, N, delta, s_bounds, l_bounds, ds_bounds, dl_bounds, s_ref, l_ref, init,
                                seg_stride=16):
         """corridor_batch on device tensors (e.g. the output of prism_bounds): s_bounds, l_bounds [B, O, N, 2],
