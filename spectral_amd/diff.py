@@ -3,11 +3,10 @@ torch.autograd graph whose backward is one btrapz_solve_vjp_device launch (inclu
 is HIP; torch only sums the per-candidate parameter gradients of a set.  spectral_amd.diff.traj_cost(...) scores the
 sampled trajectories as find_traj does (a_cost, btrapz_traj_cost_device) with a backward of one
 btrapz_traj_cost_vjp_device launch: diff.solve followed by diff.traj_cost is the reference's tuning objective."""
-import types
-
 import torch
 
 from . import layout as L
+from .solver import DeviceBatch
 
 N_PARAMS = 20   # layout.Shared.as_array() without delta
 
@@ -30,75 +29,21 @@ def _f64(t):
     return t if (t.dtype == torch.float64 and t.is_contiguous()) else t.to(torch.float64).contiguous()
 
 
-class _Solve(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, seg, init, ref_end, dl_bounds, params, solver, seg_count, set_index, variant, delta):
-        d = solver.device
-        seg, init, ref_end, dl_bounds = (_f64(t.detach()).to(d) for t in (seg, init, ref_end, dl_bounds))
-        B, S = seg.shape[1], seg.shape[2]
-        prm = params.detach().to("cpu", torch.float64)
-        rows = prm.reshape(-1, N_PARAMS).tolist()
-        sets = [shared_from_params(r, variant, delta) for r in rows]
-        o = dict(ctrl=torch.zeros((B, 12 * S), dtype=torch.float64, device=d),
-                 cost=torch.empty(B, dtype=torch.float64, device=d),
-                 status=torch.empty(B, dtype=torch.int32, device=d), iters=torch.empty(B, dtype=torch.int32, device=d))
-        if set_index is not None:
-            if seg_count is None:
-                rec = types.SimpleNamespace(B=B, S=S, seg=seg, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
-                o = solver.solve_sets(rec, sets, set_index, keep_multipliers=True, out=o)
-            else:
-                rec = dict(B=B, seg_stride=S, seg=seg, seg_count=seg_count, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
-                o = solver._sets_call(B, S, sets, set_index, rec, seg_count, o, None, True, {})
-        else:
-            o["lam"] = torch.empty((2, 36, B, S), dtype=torch.float64, device=d)
-            stream = torch.cuda.current_stream(d).cuda_stream
-            solver.ctx.solve_warm_device(B, S, sets[0], seg, seg_count, init, ref_end, dl_bounds, o["ctrl"], o["cost"],
-                                         o["status"], o["iters"], lam_out=o["lam"], stream=stream)
-        ctx.solver, ctx.sets, ctx.set_index, ctx.seg_count = solver, sets, set_index, seg_count
-        ctx.params_shape, ctx.params_device = params.shape, params.device
-        ctx.inputs = (seg, init, ref_end, dl_bounds)
-        ctx.out = o
-        ctx.mark_non_differentiable(o["status"])
-        return o["ctrl"], o["cost"], o["status"]
-
-    @staticmethod
-    def backward(ctx, ctrl_bar, cost_bar, _status_bar):
-        seg, init, ref_end, dl_bounds = ctx.inputs
-        B, S = seg.shape[1], seg.shape[2]
-        if ctrl_bar is None and cost_bar is None:
-            return (None,) * 10
-        if ctx.seg_count is None:
-            rec = types.SimpleNamespace(B=B, S=S, seg=seg, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
-        else:
-            rec = dict(B=B, seg_stride=S, seg=seg, seg_count=ctx.seg_count, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
-        g = ctx.solver.solve_vjp(rec, ctx.sets, ctx.out, ctrl_bar, cost_bar, set_index=ctx.set_index)
-        need = ctx.needs_input_grad
-        gp = None
-        if need[4]:
-            if ctx.set_index is None:
-                gp = g["shared"].sum(0)
-            else:
-                n_sets = len(ctx.sets)
-                idx = ctx.set_index.long().clamp(0, n_sets - 1)   # (unsolved candidates carry zero rows)
-                gp = torch.zeros((n_sets, N_PARAMS), dtype=torch.float64, device=g["shared"].device)
-                gp.index_add_(0, idx, g["shared"])
-            gp = gp.reshape(ctx.params_shape).to(ctx.params_device)
-        return (g["seg"] if need[0] else None, g["init"] if need[1] else None, g["ref_end"] if need[2] else None,
-                g["dl_bounds"] if need[3] else None, gp, None, None, None, None, None)
+def _on(solver, *tensors):
+    """The tensors detached, as contiguous float64 on the solver's device."""
+    return [_f64(t.detach()).to(solver.device) for t in tensors]
 
 
-def solve(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, set_index=None, variant=0, delta=0.1):
-    """Differentiable batched solve.  seg [NUM_SEG_FIELDS, B, S], init [B, 6], ref_end [B, 2], dl_bounds [B, 10]: the
-    batch (device tensors, float64); params: [20] (one set) or [n_sets, 20] with set_index (int32 [B]) -- the parameter
-    rows of shared_from_params.  seg_count: int32 [B] for a ragged batch.  Returns (ctrl [B, 12 S], cost [B], status [B]);
-    status is not differentiable.  The solve runs with its multipliers kept and no rescue pass (elastic = 0); gradients
-    are defined for candidates of status 1 or 2 and are 0 elsewhere (btrapz_solve_vjp_device).  Field 0 of seg (the
-    segment durations) gets no gradient."""
+def _check_params(params, set_index):
     if set_index is None and params.dim() != 1:
         raise ValueError("params must be [20] without set_index, [n_sets, 20] with it")
     if params.shape[-1] != N_PARAMS:
         raise ValueError("params rows have %d entries (layout.Shared.as_array() without delta)" % N_PARAMS)
-    return _Solve.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, set_index, variant, delta)
+
+
+def _sets_of_params(params, variant, delta):
+    """Parameter rows [20] or [n_sets, 20] -> list of layout.Shared."""
+    return [shared_from_params(r, variant, delta) for r in params.detach().to("cpu", torch.float64).reshape(-1, N_PARAMS).tolist()]
 
 
 def _sum_rows(g, set_index, n_sets):
@@ -111,16 +56,55 @@ def _sum_rows(g, set_index, n_sets):
     return out
 
 
+def _solve_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, set_index, variant, delta):
+    """(record, sets, result dict) of the solve with its multipliers kept and no rescue pass; ctrl starts zeroed."""
+    rec = DeviceBatch.from_tensors(*_on(solver, seg, init, ref_end, dl_bounds), seg_count=seg_count)
+    sets = _sets_of_params(params, variant, delta)
+    o = solver.new_result(rec.B, rec.S, zero_ctrl=True)
+    if set_index is not None:
+        return rec, sets, solver.solve_sets(rec, sets, set_index, keep_multipliers=True, out=o)
+    return rec, sets, solver.solve(rec, sets[0], keep_multipliers=True, out=o)
+
+
+class _Solve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, seg, init, ref_end, dl_bounds, params, solver, seg_count, set_index, variant, delta):
+        ctx.rec, ctx.sets, o = _solve_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, set_index, variant, delta)
+        ctx.solver, ctx.set_index, ctx.out = solver, set_index, o
+        ctx.params_shape, ctx.params_device = params.shape, params.device
+        ctx.mark_non_differentiable(o["status"])
+        return o["ctrl"], o["cost"], o["status"]
+
+    @staticmethod
+    def backward(ctx, ctrl_bar, cost_bar, _status_bar):
+        if ctrl_bar is None and cost_bar is None:
+            return (None,) * 10
+        g = ctx.solver.solve_vjp(ctx.rec, ctx.sets, ctx.out, ctrl_bar, cost_bar, set_index=ctx.set_index)
+        need = ctx.needs_input_grad
+        gp = None
+        if need[4]:
+            gp = _sum_rows(g["shared"], ctx.set_index, len(ctx.sets)).reshape(ctx.params_shape).to(ctx.params_device)
+        return (g["seg"] if need[0] else None, g["init"] if need[1] else None, g["ref_end"] if need[2] else None,
+                g["dl_bounds"] if need[3] else None, gp, None, None, None, None, None)
+
+
+def solve(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, set_index=None, variant=0, delta=0.1):
+    """Differentiable batched solve.  seg [NUM_SEG_FIELDS, B, S], init [B, 6], ref_end [B, 2], dl_bounds [B, 10]: the
+    batch (device tensors, float64); params: [20] (one set) or [n_sets, 20] with set_index (int32 [B]) -- the parameter
+    rows of shared_from_params.  seg_count: int32 [B] for a ragged batch.  Returns (ctrl [B, 12 S], cost [B], status [B]);
+    status is not differentiable.  The solve runs with its multipliers kept and no rescue pass (elastic = 0); gradients
+    are defined for candidates of status 1 or 2 and are 0 elsewhere (btrapz_solve_vjp_device).  Field 0 of seg (the
+    segment durations) gets no gradient."""
+    _check_params(params, set_index)
+    return _Solve.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, set_index, variant, delta)
+
+
 class _TrajCost(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctrl, init, params, s_ref, l_ref, seg, solver, seg_count, set_index, status, variant, delta):
-        d = solver.device
-        ctrl_d, init_d, seg_d = (_f64(t.detach()).to(d) for t in (ctrl, init, seg))
-        s_d, l_d = (_f64(t.detach()).to(d) for t in (s_ref, l_ref))
-        B, S = seg_d.shape[1], seg_d.shape[2]
-        rows = params.detach().to("cpu", torch.float64).reshape(-1, N_PARAMS).tolist()
-        sets = [shared_from_params(r, variant, delta) for r in rows]
-        rec = dict(B=B, seg_stride=S, seg=seg_d, seg_count=seg_count, init=init_d)
+        ctrl_d, init_d, seg_d, s_d, l_d = _on(solver, ctrl, init, seg, s_ref, l_ref)
+        sets = _sets_of_params(params, variant, delta)
+        rec = DeviceBatch.from_tensors(seg_d, init_d, seg_count=seg_count)
         cost, _ = solver.traj_cost(rec, sets, ctrl_d, s_d, l_d, status=status, set_index=set_index)
         ctx.solver, ctx.sets, ctx.rec, ctx.set_index, ctx.status = solver, sets, rec, set_index, status
         ctx.arrays = (ctrl_d, s_d, l_d)
@@ -132,7 +116,7 @@ class _TrajCost(torch.autograd.Function):
         if cost_bar is None:
             return (None,) * 12
         ctrl_d, s_d, l_d = ctx.arrays
-        B = ctx.rec["B"]
+        B = ctx.rec.B
         # a candidate that is not scored has cost +inf and a zero gradient: its cotangent must not turn that into NaN
         g = ctx.solver.traj_cost_vjp(ctx.rec, ctx.sets, ctrl_d, s_d, l_d, cost_bar.reshape(B), status=ctx.status,
                                      set_index=ctx.set_index)
@@ -155,10 +139,7 @@ def traj_cost(ctrl, seg, init, s_ref, l_ref, params, solver, seg_count=None, set
     not scored).  Gradients flow to ctrl, init, params (summed over a set's rows), s_ref and l_ref; the durations are not
     differentiated.  When the same params tensor also feeds diff.solve, autograd adds the explicit part and the part
     through the solve."""
-    if set_index is None and params.dim() != 1:
-        raise ValueError("params must be [20] without set_index, [n_sets, 20] with it")
-    if params.shape[-1] != N_PARAMS:
-        raise ValueError("params rows have %d entries (layout.Shared.as_array() without delta)" % N_PARAMS)
+    _check_params(params, set_index)
     return _TrajCost.apply(ctrl, init, params, s_ref, l_ref, seg, solver, seg_count, set_index, status, variant, delta)
 
 
@@ -185,20 +166,11 @@ class _Sample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctrl, init, seg, solver, seg_count, sel, delta):
         d = solver.device
-        ctrl_d, init_d, seg_d = (_f64(t.detach()).to(d) for t in (ctrl, init, seg))
-        B, S = seg_d.shape[1], seg_d.shape[2]
-        sel = (torch.arange(B, device=d) if sel is None else sel).to(d, dtype=torch.int64).contiguous()
-        if seg_count is None:
-            out, npts = solver.sample(types.SimpleNamespace(B=B, S=S, seg=seg_d, init=init_d), ctrl_d, sel, delta)
-        else:
-            t = seg_d[L.F_T] * (torch.arange(S, device=d)[None, :] < seg_count[:, None])
-            max_points = int(torch.floor(t / delta + 1e-9).sum(1).max().item()) + 2
-            out = torch.zeros((sel.numel(), 6, max_points), dtype=torch.float64, device=d)
-            npts = torch.zeros(sel.numel(), dtype=torch.int32, device=d)
-            solver.ctx.sample_ragged_device(B, S, seg_count, delta, seg_d, init_d, ctrl_d, sel, max_points, out, npts,
-                                            stream=torch.cuda.current_stream(d).cuda_stream)
-        ctx.solver, ctx.sel, ctx.delta = solver, sel, delta
-        ctx.rec = dict(B=B, seg_stride=S, seg=seg_d, seg_count=seg_count)
+        ctrl_d, init_d, seg_d = _on(solver, ctrl, init, seg)
+        rec = DeviceBatch.from_tensors(seg_d, init_d, seg_count=seg_count)
+        sel = (torch.arange(rec.B, device=d) if sel is None else sel).to(d, dtype=torch.int64).contiguous()
+        out, npts = solver.sample(rec, ctrl_d, sel, delta)
+        ctx.solver, ctx.sel, ctx.delta, ctx.rec = solver, sel, delta, rec
         ctx.mark_non_differentiable(npts)
         return out, npts
 
@@ -208,7 +180,7 @@ class _Sample(torch.autograd.Function):
             return (None,) * 7
         need = ctx.needs_input_grad
         g = ctx.solver.sample_vjp(ctx.rec, ctx.sel, ctx.delta, out_bar, want_ctrl=need[0], want_init=need[1])
-        B = ctx.rec["B"]
+        B = ctx.rec.B
         return (_sum_selections(g["ctrl"], ctx.sel, B) if need[0] else None,
                 _sum_selections(g["init"], ctx.sel, B) if need[1] else None, None, None, None, None, None)
 
@@ -226,18 +198,9 @@ def sample(ctrl, seg, init, solver, seg_count=None, sel=None, delta=0.1):
 class _EvalStates(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctrl, times, seg, solver, seg_count):
-        d = solver.device
-        ctrl_d, times_d, seg_d = (_f64(t.detach()).to(d) for t in (ctrl, times, seg))
-        B, S = seg_d.shape[1], seg_d.shape[2]
-        if seg_count is None:
-            x = solver.eval_states(types.SimpleNamespace(B=B, S=S, seg=seg_d), ctrl_d, times_d)
-        else:
-            n = times_d.shape[1]
-            x = torch.empty((B, 2, n, 3), dtype=torch.float64, device=d)
-            solver.ctx.eval_states_device(B, S, seg_count, seg_d, ctrl_d, n, times_d, x,
-                                          stream=torch.cuda.current_stream(d).cuda_stream)
-        ctx.solver = solver
-        ctx.rec = dict(B=B, seg_stride=S, seg=seg_d, seg_count=seg_count)
+        ctrl_d, times_d, seg_d = _on(solver, ctrl, times, seg)
+        ctx.solver, ctx.rec = solver, DeviceBatch.from_tensors(seg_d, seg_count=seg_count)
+        x = solver.eval_states(ctx.rec, ctrl_d, times_d)
         ctx.arrays = (ctrl_d, times_d)
         ctx.times_shape = times.shape
         return x
@@ -263,32 +226,10 @@ def eval_states(ctrl, seg, times, solver, seg_count=None):
 
 # ---- forward mode: Jacobian-vector products (btrapz_solve_jvp_device) --------------------------------------------------
 
-def _record(seg, init, ref_end, dl_bounds, seg_count):
-    B, S = seg.shape[1], seg.shape[2]
-    if seg_count is None:
-        return types.SimpleNamespace(B=B, S=S, seg=seg, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
-    return dict(B=B, seg_stride=S, seg=seg, seg_count=seg_count, init=init, ref_end=ref_end, dl_bounds=dl_bounds)
-
-
 def solve_kept(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, set_index=None, variant=0, delta=0.1):
     """The solve of diff.solve without a graph: multipliers kept, no rescue pass.  Returns the result dict ("ctrl", "cost",
     "status", "iters", "lam"): what solve_jacobian(out=...) and BatchSolver.solve_jvp / solve_vjp take."""
-    d = solver.device
-    seg, init, ref_end, dl_bounds = (_f64(t.detach()).to(d) for t in (seg, init, ref_end, dl_bounds))
-    B, S = seg.shape[1], seg.shape[2]
-    sets = [shared_from_params(r, variant, delta) for r in params.detach().to("cpu", torch.float64).reshape(-1, N_PARAMS).tolist()]
-    o = dict(ctrl=torch.zeros((B, 12 * S), dtype=torch.float64, device=d), cost=torch.empty(B, dtype=torch.float64, device=d),
-             status=torch.empty(B, dtype=torch.int32, device=d), iters=torch.empty(B, dtype=torch.int32, device=d))
-    rec = _record(seg, init, ref_end, dl_bounds, seg_count)
-    if set_index is not None and seg_count is None:
-        o = solver.solve_sets(rec, sets, set_index, keep_multipliers=True, out=o)
-    elif set_index is not None:
-        o = solver.solve_sets_ragged(rec, sets, set_index, keep_multipliers=True)
-    else:
-        o["lam"] = torch.empty((2, 36, B, S), dtype=torch.float64, device=d)
-        solver.ctx.solve_warm_device(B, S, sets[0], seg, seg_count, init, ref_end, dl_bounds, o["ctrl"], o["cost"],
-                                     o["status"], o["iters"], lam_out=o["lam"], stream=torch.cuda.current_stream(d).cuda_stream)
-    return o
+    return _solve_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, set_index, variant, delta)[2]
 
 
 def solve_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, *, seg_count=None, set_index=None, variant=0,
@@ -304,10 +245,7 @@ def solve_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, *, se
     step accepted).  PRECONDITION: `out` is the solve of exactly these inputs, params, seg_count, set_index, variant and
     delta.  Nothing can check that: the derivative is stated at out["ctrl"] with the active set of out["lam"], and with
     another problem's arrays it is the derivative of nothing, returned without an error.  Only the shapes are checked."""
-    if set_index is None and params.dim() != 1:
-        raise ValueError("params must be [20] without set_index, [n_sets, 20] with it")
-    if params.shape[-1] != N_PARAMS:
-        raise ValueError("params rows have %d entries (layout.Shared.as_array() without delta)" % N_PARAMS)
+    _check_params(params, set_index)
     if out is not None:
         B_, S_ = seg.shape[1], seg.shape[2]
         if out.get("lam") is None or tuple(out["ctrl"].shape) != (B_, 12 * S_) or tuple(out["lam"].shape) != (2, 36, B_, S_) \
@@ -317,19 +255,19 @@ def solve_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, *, se
     if not columns or min(columns) < 0 or max(columns) >= N_PARAMS:
         raise ValueError("columns: at least one, each in [0, %d)" % N_PARAMS)
     d = solver.device
-    seg, init, ref_end, dl_bounds = (_f64(t.detach()).to(d) for t in (seg, init, ref_end, dl_bounds))
-    B = seg.shape[1]
+    rec = DeviceBatch.from_tensors(*_on(solver, seg, init, ref_end, dl_bounds), seg_count=seg_count)
+    B = rec.B
     if out is None:
-        out = solve_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count=seg_count, set_index=set_index,
-                         variant=variant, delta=delta)
+        out = solve_kept(solver, rec.seg, rec.init, rec.ref_end, rec.dl_bounds, params, seg_count=seg_count,
+                         set_index=set_index, variant=variant, delta=delta)
     rows = params.detach().to(d, torch.float64).reshape(-1, N_PARAMS)
-    sets = [shared_from_params(r, variant, delta) for r in rows.tolist()]
+    sets = _sets_of_params(params, variant, delta)
     T = len(columns)
     tan = torch.zeros((T, B, N_PARAMS), dtype=torch.float64, device=d)
     per_cand = rows[set_index.long().clamp(0, rows.shape[0] - 1)] if set_index is not None else rows[:1].expand(B, N_PARAMS)
     for t, c in enumerate(columns):
         tan[t, :, c] = per_cand[:, c] if log else 1.0
-    j = solver.solve_jvp(_record(seg, init, ref_end, dl_bounds, seg_count), sets, out, {"shared": tan}, set_index=set_index)
+    j = solver.solve_jvp(rec, sets, out, {"shared": tan}, set_index=set_index)
     return dict(ctrl=out["ctrl"], cost=out["cost"], status=out["status"], dctrl=j["ctrl"], dcost=j["cost"], out=out)
 
 
@@ -338,9 +276,9 @@ def sample_jvp(solver, dctrl, seg, dinit=None, seg_count=None, sel=None, delta=0
     forward kernel applied to the tangents: dctrl [T, B, 12 S] and dinit [T, B, 6] (None: zero) -> [T, nsel, 6, max_points],
     one launch over the T B tangent candidates (seg, seg_count and sel as diff.sample, repeated per tangent)."""
     d = solver.device
-    dctrl, seg = _f64(dctrl.detach()).to(d), _f64(seg.detach()).to(d)
+    dctrl, seg = _on(solver, dctrl, seg)
     T, B = dctrl.shape[0], dctrl.shape[1]
-    di = torch.zeros((T * B, 6), dtype=torch.float64, device=d) if dinit is None else _f64(dinit.detach()).to(d).reshape(T * B, 6)
+    di = torch.zeros((T * B, 6), dtype=torch.float64, device=d) if dinit is None else _on(solver, dinit)[0].reshape(T * B, 6)
     sel = (torch.arange(B, device=d) if sel is None else sel.to(d)).to(torch.int64)
     sel_rep = (sel[None, :] + B * torch.arange(T, device=d)[:, None]).reshape(-1)
     cnt = None if seg_count is None else seg_count.repeat(T).contiguous()
@@ -352,8 +290,7 @@ def sample_jvp(solver, dctrl, seg, dinit=None, seg_count=None, sel=None, delta=0
 def eval_states_jvp(solver, dctrl, seg, times, seg_count=None):
     """Tangents of the evaluated states.  State evaluation is linear in ctrl at fixed times, so its Jacobian-vector product
     is the forward kernel applied to the tangents: dctrl [T, B, 12 S], times [B, n_times] -> [T, B, 2, n_times, 3]."""
-    d = solver.device
-    dctrl, seg, times = _f64(dctrl.detach()).to(d), _f64(seg.detach()).to(d), _f64(times.detach()).to(d)
+    dctrl, seg, times = _on(solver, dctrl, seg, times)
     T, B = dctrl.shape[0], dctrl.shape[1]
     cnt = None if seg_count is None else seg_count.repeat(T).contiguous()
     with torch.no_grad():
@@ -365,7 +302,7 @@ class _Corridor(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, solver, variant, delta, seg_stride):
         d = solver.device
-        ins = [_f64(t.detach()).to(d) for t in (s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref)]
+        ins = _on(solver, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref)
         B, N = ins[0].shape[0], ins[0].shape[2]
         init = torch.zeros((B, 6), dtype=torch.float64, device=d)   # (the stage does not read it)
         rec = solver.corridor_batch_tensors(variant, N, delta, *ins, init, seg_stride=seg_stride)
@@ -397,7 +334,7 @@ def corridor(solver, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_re
 class _PrismBounds(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prisms, solver, N, O, road):
-        p = _f64(prisms.detach()).to(solver.device)
+        p, = _on(solver, prisms)
         sb, lb, n = solver.prism_bounds(p, N, O, road=road)
         ctx.solver, ctx.prisms, ctx.N, ctx.O, ctx.road = solver, p, N, O, road
         ctx.shape, ctx.device_in = prisms.shape, prisms.device

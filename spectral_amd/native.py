@@ -142,21 +142,107 @@ class CRoad(C.Structure):
         return cls(0.0, 50.0, -2.0, 8.0, 5.0 / 3 + 5.0 / 3, 2.0 / 3 + 2.0 / 3, 10.0)
 
 
-EXPORTS = ("btrapz_corridor_from_file", "btrapz_find_traj", "btrapz_create", "btrapz_destroy", "btrapz_last_error",
-           "btrapz_device_count", "btrapz_solve_batch_device", "btrapz_argmin_device",
-           "btrapz_sample_device", "btrapz_solve_batch_host", "btrapz_solve_ragged_device",
-           "btrapz_corridor_batch_device", "btrapz_corridor_batch_vjp_device", "btrapz_corridor_vjp_host", "btrapz_sample_ragged_device", "btrapz_solve_warm_device",
-           "btrapz_solve_sets_device", "btrapz_solve_vjp_device", "btrapz_solve_jvp_device", "btrapz_traj_cost_device", "btrapz_traj_cost_vjp_device",
-           "btrapz_eval_states_device", "btrapz_sample_vjp_device", "btrapz_eval_states_vjp_device", "btrapz_find_traj_mem", "btrapz_find_traj_mem_cap", "btrapz_prism_bounds_device",
-           "btrapz_prism_corridor_batch_device", "btrapz_prism_bounds_vjp_device", "btrapz_prism_bounds_vjp_host",
-           "btrapz_find_traj_last_iterations", "btrapz_argmin_pairs_device", "btrapz_options_init",
-           "btrapz_rescue_violations_device", "btrapz_find_traj_last_status", "btrapz_debug_mqm_tables",
-           "btrapz_debug_axis_records", "btrapz_debug_resume_keys", "btrapz_debug_parse_double", "btrapz_debug_format_fixed",
-           "btrapz_last_solve_form", "btrapz_build_has_experiments", "btrapz_workspace_bytes",
-           "btrapz_multi_create", "btrapz_multi_destroy", "btrapz_multi_last_error", "btrapz_multi_transport",
-           "btrapz_multi_transport_library", "btrapz_multi_device_count", "btrapz_multi_shard_bounds", "btrapz_multi_upload",
-           "btrapz_multi_set_shards", "btrapz_multi_solve_argmin", "btrapz_multi_result", "btrapz_multi_wait",
-           "btrapz_multi_shard_view", "btrapz_multi_download")
+_i, _d, _ll, _vp, _str = C.c_int, C.c_double, C.c_longlong, C.c_void_p, C.c_char_p
+_ip, _sh, _opt, _par, _road = C.POINTER(C.c_int), C.POINTER(CShared), C.POINTER(COptions), C.POINTER(CParams), C.POINTER(CRoad)
+_batch = [_vp] * 4          # seg, init, ref_end, dl_bounds of a uniform batch
+_ragged = [_vp] * 5         # seg, seg_count, init, ref_end, dl_bounds
+_result = [_vp] * 4         # ctrl, cost, status, iters
+_knots = [_vp] * 6          # s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref
+
+# Every function of include/btrapz_hip.h: name -> (restype, argtypes), applied by lib().  tests/test_abi.py holds the
+# argument counts and return types to the header's prototypes (a wrong count in ctypes is silent garbage, not an error).
+PROTOTYPES = {
+    "btrapz_find_traj": (_d, [_i, _str, _str, _par]),
+    "btrapz_find_traj_mem": (_d, [_i, C.POINTER(CTrajInput), _par, _i, _vp, _ip, _vp, _ip]),
+    "btrapz_find_traj_mem_cap": (_d, [_i, C.POINTER(CTrajInput), _par, _i, _vp, _ip, _vp, _i, _ip]),
+    "btrapz_find_traj_last_iterations": (_i, []),
+    "btrapz_find_traj_last_status": (_i, [_vp]),
+    "btrapz_corridor_from_file": (_i, [_i, _str, C.POINTER(CSegment), _i]),
+    "btrapz_options_init": (None, [_opt]),
+    "btrapz_create": (_i, [C.POINTER(_vp), _i]),
+    "btrapz_destroy": (_i, [_vp]),
+    "btrapz_last_error": (_str, [_vp]),
+    "btrapz_workspace_bytes": (_ll, [_vp]),
+    "btrapz_device_count": (_i, []),
+    "btrapz_build_has_experiments": (_i, []),
+    "btrapz_solve_batch_device": (_i, [_vp, _sh, _opt, _i, _i] + _batch + _result + [_vp]),
+    "btrapz_solve_batch_host": (_i, [_vp, _sh, _opt, _i, _i] + _batch + _result),
+    "btrapz_rescue_violations_device": (_i, [_vp, _i, _vp, _vp]),
+    "btrapz_last_solve_form": (_i, [_vp]),
+    "btrapz_argmin_device": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp, _vp]),
+    "btrapz_argmin_pairs_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_multi_create": (_i, [C.POINTER(_vp), _ip, _i, _i]),
+    "btrapz_multi_destroy": (_i, [_vp]),
+    "btrapz_multi_last_error": (_str, [_vp]),
+    "btrapz_multi_transport": (_i, [_vp]),
+    "btrapz_multi_transport_library": (_str, [_vp]),
+    "btrapz_multi_device_count": (_i, [_vp]),
+    "btrapz_multi_shard_bounds": (_i, [_i, _i, _i, _i, _ip, _ip]),
+    "btrapz_multi_upload": (_i, [_vp, _i, _i, _i] + _batch),
+    "btrapz_multi_set_shards": (_i, [_vp, _i, _i, _i, C.POINTER(CMultiShard)]),
+    "btrapz_multi_solve_argmin": (_i, [_vp, _sh, _opt]),
+    "btrapz_multi_result": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "btrapz_multi_wait": (_i, [_vp]),
+    "btrapz_multi_shard_view": (_i, [_vp, _i, C.POINTER(CMultiView)]),
+    "btrapz_multi_download": (_i, [_vp] + _result),
+    "btrapz_sample_device": (_i, [_vp, _i, _i, _d, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "btrapz_sample_ragged_device": (_i, [_vp, _i, _i, _vp, _d, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "btrapz_solve_ragged_device": (_i, [_vp, _sh, _opt, _i, _i] + _ragged + _result + [_vp]),
+    "btrapz_corridor_batch_device": (_i, [_vp, _i, _i, _i, _i, _d] + _knots + [_i, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_corridor_batch_vjp_device": (_i, [_vp, _i, _i, _i, _i, _d] + _knots + [_i, _vp, _vp, _vp, C.POINTER(CKnotGrads), _vp]),
+    "btrapz_corridor_vjp_host": (_i, [_i, _i, _i, _d] + _knots + [_i, _vp, _vp, _vp, C.POINTER(CKnotGrads), _ip]),
+    "btrapz_prism_bounds_device": (_i, [_vp, _i, _i, _i, _road, _vp, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_prism_bounds_vjp_device": (_i, [_vp, _i, _i, _i, _road, _vp, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_prism_bounds_vjp_host": (_i, [_i, _i, _i, _road, _vp, _i, _vp, _vp, _vp]),
+    "btrapz_prism_corridor_batch_device": (_i, [_vp, _i, _i, _i, _i, _road, _vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
+                                                _vp, _vp, _vp]),
+    "btrapz_solve_warm_device": (_i, [_vp, _sh, _opt, C.POINTER(CWarm), _i, _i] + _ragged + _result + [_vp]),
+    "btrapz_solve_sets_device": (_i, [_vp, _sh, _i, _vp, _opt, C.POINTER(CWarm), _i, _i] + _ragged + _result + [_vp]),
+    "btrapz_solve_vjp_device": (_i, [_vp, _sh, _i, _vp, _i, _i] + _ragged + [_vp, _vp, _vp, _vp, _vp, C.POINTER(CGrads), _vp]),
+    "btrapz_solve_jvp_device": (_i, [_vp, _sh, _i, _vp, _i, _i] + _ragged + [_vp, _vp, _vp, _i, C.POINTER(CTangents), _vp, _vp,
+                                     _vp]),
+    "btrapz_traj_cost_device": (_i, [_vp, _sh, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "btrapz_traj_cost_vjp_device": (_i, [_vp, _sh, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i] + [_vp] * 7),
+    "btrapz_eval_states_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "btrapz_sample_vjp_device": (_i, [_vp, _i, _i, _vp, _d, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_eval_states_vjp_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_debug_mqm_tables": (_i, [_vp, _sh, _vp, _vp]),
+    "btrapz_debug_axis_records": (_i, [_vp, _i, _vp, _vp]),
+    "btrapz_debug_resume_keys": (_i, [_vp, _i, _vp]),
+    "btrapz_debug_parse_double": (_d, [_str, _ip]),
+    "btrapz_debug_format_fixed": (_i, [_d, _str]),
+}
+EXPORTS = tuple(PROTOTYPES)
+
+
+def _ptr(t):
+    """Device tensor -> its address as a c_void_p; None -> None (a NULL argument or struct field), always.  Keeps nothing
+    alive: the caller holds the tensor until the launch has run."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _np_ptr(a):
+    """The same for a numpy array (host pointers)."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _np_f64(a):
+    """Array-like -> contiguous float64 numpy array (referenced, not copied, when it is one already); None -> None."""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _stream(stream):
+    """The hipStream_t argument: a stream's handle as an integer, None or 0 = the default stream."""
+    return C.c_void_p(stream or 0)
+
+
+def _sets_array(sets):
+    """list of layout.Shared -> btrapz_shared[n_sets] (host array; at least one slot, so that an empty list has an address)."""
+    return (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
+
+
+def _warm(x0, lam0, lam_out, mu0, smin, hint):
+    return CWarm(_ptr(x0), _ptr(lam0), _ptr(lam_out), float(mu0), float(smin), _ptr(hint))
 
 
 def build(verbose=False):
@@ -206,80 +292,9 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        vp, dp, ip, llp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
-        l.btrapz_find_traj.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.POINTER(CParams)]
-        l.btrapz_find_traj.restype = C.c_double
-        l.btrapz_find_traj_mem.argtypes = [C.c_int, C.POINTER(CTrajInput), C.POINTER(CParams), C.c_int, C.c_void_p,
-                                           C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
-        l.btrapz_find_traj_mem.restype = C.c_double
-        l.btrapz_find_traj_mem_cap.argtypes = [C.c_int, C.POINTER(CTrajInput), C.POINTER(CParams), C.c_int, C.c_void_p,
-                                               C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        l.btrapz_find_traj_mem_cap.restype = C.c_double
-        l.btrapz_corridor_from_file.argtypes = [C.c_int, C.c_char_p, C.POINTER(CSegment), C.c_int]
-        l.btrapz_corridor_from_file.restype = C.c_int
-        l.btrapz_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-        l.btrapz_destroy.argtypes = [C.c_void_p]
-        l.btrapz_last_error.argtypes = [C.c_void_p]; l.btrapz_last_error.restype = C.c_char_p
-        l.btrapz_device_count.restype = C.c_int
-        l.btrapz_find_traj_last_iterations.restype = C.c_int
-        l.btrapz_find_traj_last_status.argtypes = [C.c_void_p]; l.btrapz_find_traj_last_status.restype = C.c_int
-        l.btrapz_options_init.argtypes = [C.POINTER(COptions)]; l.btrapz_options_init.restype = None
-        l.btrapz_rescue_violations_device.argtypes = [vp, C.c_int, dp, vp]
-        l.btrapz_last_solve_form.argtypes = [vp]; l.btrapz_last_solve_form.restype = C.c_int
-        l.btrapz_workspace_bytes.argtypes = [vp]; l.btrapz_workspace_bytes.restype = C.c_longlong
-        l.btrapz_debug_mqm_tables.argtypes = [vp, C.POINTER(CShared), dp, dp]
-        l.btrapz_solve_batch_device.argtypes = [vp, C.POINTER(CShared), C.POINTER(COptions), C.c_int, C.c_int,
-                                                dp, dp, dp, dp, dp, dp, ip, ip, vp]
-        l.btrapz_argmin_device.argtypes = [vp, C.c_int, C.c_int, C.c_longlong, dp, llp, dp, vp]
-        l.btrapz_argmin_pairs_device.argtypes = [vp, C.c_int, C.c_int, llp, dp, llp, vp]
-        l.btrapz_sample_device.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, dp, dp, C.c_int, llp, C.c_int,
-                                           dp, ip, vp]
-        l.btrapz_solve_batch_host.argtypes = [vp, C.POINTER(CShared), C.POINTER(COptions), C.c_int, C.c_int,
-                                              dp, dp, dp, dp, dp, dp, ip, ip]
-        l.btrapz_solve_ragged_device.argtypes = [vp, C.POINTER(CShared), C.POINTER(COptions), C.c_int, C.c_int,
-                                                 dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
-        l.btrapz_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
-                                                   dp, dp, dp, dp, dp, dp, C.c_int, dp, ip, dp, dp, vp]
-        l.btrapz_corridor_batch_vjp_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
-                                                       dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp, C.POINTER(CKnotGrads), vp]
-        l.btrapz_corridor_vjp_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, dp, dp, dp, dp, dp, dp, C.c_int,
-                                               dp, dp, dp, C.POINTER(CKnotGrads), C.POINTER(C.c_int)]
-        l.btrapz_sample_ragged_device.argtypes = [vp, C.c_int, C.c_int, ip, C.c_double, dp, dp, dp, C.c_int, llp,
-                                                  C.c_int, dp, ip, vp]
-        l.btrapz_solve_warm_device.argtypes = [vp, C.POINTER(CShared), C.POINTER(COptions), C.POINTER(CWarm), C.c_int,
-                                               C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
-        l.btrapz_solve_sets_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.POINTER(COptions), C.POINTER(CWarm),
-                                               C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, dp, ip, ip, vp]
-        l.btrapz_solve_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, dp,
-                                              dp, dp, ip, dp, dp, C.POINTER(CGrads), vp]
-        l.btrapz_solve_jvp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, dp,
-                                              dp, dp, ip, C.c_int, C.POINTER(CTangents), dp, dp, vp]
-        l.btrapz_traj_cost_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, ip,
-                                              C.c_int, dp, dp, C.c_int, dp, ip, vp]
-        l.btrapz_traj_cost_vjp_device.argtypes = [vp, C.POINTER(CShared), C.c_int, ip, C.c_int, C.c_int, dp, ip, dp, dp, ip,
-                                                  C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, dp, vp]
-        l.btrapz_eval_states_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, vp]
-        l.btrapz_sample_vjp_device.argtypes = [vp, C.c_int, C.c_int, ip, C.c_double, dp, C.c_int, llp, C.c_int, dp, dp, dp, vp]
-        l.btrapz_eval_states_vjp_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, dp, dp, dp, dp, vp]
-        l.btrapz_prism_bounds_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, ip, vp]
-        l.btrapz_prism_bounds_vjp_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, dp, vp]
-        l.btrapz_prism_bounds_vjp_host.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int, dp, dp, dp]
-        l.btrapz_prism_corridor_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRoad), dp, C.c_int,
-                                                         C.c_double, dp, dp, dp, dp, C.c_int, dp, ip, dp, dp, ip, vp]
-        l.btrapz_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int]
-        l.btrapz_multi_destroy.argtypes = [vp]
-        l.btrapz_multi_last_error.argtypes = [vp]; l.btrapz_multi_last_error.restype = C.c_char_p
-        l.btrapz_multi_transport.argtypes = [vp]
-        l.btrapz_multi_transport_library.argtypes = [vp]; l.btrapz_multi_transport_library.restype = C.c_char_p
-        l.btrapz_multi_device_count.argtypes = [vp]
-        l.btrapz_multi_shard_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        l.btrapz_multi_upload.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp]
-        l.btrapz_multi_set_shards.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CMultiShard)]
-        l.btrapz_multi_solve_argmin.argtypes = [vp, C.POINTER(CShared), C.POINTER(COptions)]
-        l.btrapz_multi_result.argtypes = [vp, C.c_int, llp, dp, dp]
-        l.btrapz_multi_wait.argtypes = [vp]
-        l.btrapz_multi_shard_view.argtypes = [vp, C.c_int, C.POINTER(CMultiView)]
-        l.btrapz_multi_download.argtypes = [vp, dp, dp, ip, ip]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = l
     return _lib
 
@@ -331,33 +346,29 @@ class MultiContext:
         return lib().btrapz_multi_last_error(self._h).decode()
 
     def upload(self, batch, group=0):
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        seg, init, ref_end, dlb = f(batch.seg), f(batch.init), f(batch.ref_end), f(batch.dl_bounds)
+        seg, init, ref_end, dlb = _np_f64(batch.seg), _np_f64(batch.init), _np_f64(batch.ref_end), _np_f64(batch.dl_bounds)
         assert seg.shape == (L.NUM_SEG_FIELDS, batch.B, batch.S)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._check(lib().btrapz_multi_upload(self._h, batch.B, batch.S, int(group), p(seg), p(init), p(ref_end), p(dlb)), "btrapz_multi_upload")
+        self._check(lib().btrapz_multi_upload(self._h, batch.B, batch.S, int(group), _np_ptr(seg), _np_ptr(init),
+                                              _np_ptr(ref_end), _np_ptr(dlb)), "btrapz_multi_upload")
         self.B, self.S, self.group = batch.B, batch.S, int(group)
 
     def set_shards(self, B, S, shards, group=0):
         """shards: list of (B_g, index_base, seg, init, ref_end, dl_bounds) with torch tensors on the slot's device (or
         None for an empty shard); the tensors must stay alive while steps run."""
         arr = (CMultiShard * self.G)()
-        ptr = lambda t: t.data_ptr() if t is not None else None
         for g, (Bg, base, seg, init, ref_end, dlb) in enumerate(shards):
-            arr[g] = CMultiShard(int(Bg), int(base), ptr(seg), ptr(init), ptr(ref_end), ptr(dlb))
+            arr[g] = CMultiShard(int(Bg), int(base), _ptr(seg), _ptr(init), _ptr(ref_end), _ptr(dlb))
         self._check(lib().btrapz_multi_set_shards(self._h, int(B), int(S), int(group), arr), "btrapz_multi_set_shards")
         self.B, self.S, self.group = int(B), int(S), int(group)
         self._keep = shards
 
     def solve_argmin(self, shared, **options):
-        sh = CShared.from_shared(shared)
-        opt = _options(options.pop("max_iter", 0), options.pop("eps", 0.0), options.pop("elastic", 0), options.pop("elastic_tol", 0.0), **options)
-        self._check(lib().btrapz_multi_solve_argmin(self._h, C.byref(sh), C.byref(opt)), "btrapz_multi_solve_argmin")
+        self.prepared_step(shared, **options)()
 
     def prepared_step(self, shared, **options):
         """solve_argmin with its argument structs built once: returns a function of no arguments (timing loops)."""
         sh = CShared.from_shared(shared)
-        opt = _options(options.pop("max_iter", 0), options.pop("eps", 0.0), options.pop("elastic", 0), options.pop("elastic_tol", 0.0), **options)
+        opt = _options(**options)
         fn, check, h = lib().btrapz_multi_solve_argmin, self._check, self._h
         args = (h, C.byref(sh), C.byref(opt))
 
@@ -369,7 +380,7 @@ class MultiContext:
         """(best_idx, best_cost, best_ctrl): scalars + [12 S] for one arg-min group, arrays [n], [n], [n, 12 S] for n groups."""
         n = 1 if (self.group == 0 or self.group >= self.B) else self.B // self.group
         idx = np.zeros(n, dtype=np.int64); cost = np.zeros(n); ctrl = np.zeros((n, 12 * self.S))
-        self._check(lib().btrapz_multi_result(self._h, int(device_slot), idx.ctypes.data, cost.ctypes.data, ctrl.ctypes.data), "btrapz_multi_result")
+        self._check(lib().btrapz_multi_result(self._h, int(device_slot), _np_ptr(idx), _np_ptr(cost), _np_ptr(ctrl)), "btrapz_multi_result")
         return (int(idx[0]), float(cost[0]), ctrl[0]) if n == 1 else (idx, cost, ctrl)
 
     def wait(self):
@@ -383,7 +394,7 @@ class MultiContext:
     def download(self):
         ctrl = np.zeros((self.B, 12 * self.S)); cost = np.zeros(self.B)
         status = np.zeros(self.B, dtype=np.int32); iters = np.zeros(self.B, dtype=np.int32)
-        self._check(lib().btrapz_multi_download(self._h, ctrl.ctypes.data, cost.ctypes.data, status.ctypes.data, iters.ctypes.data), "btrapz_multi_download")
+        self._check(lib().btrapz_multi_download(self._h, _np_ptr(ctrl), _np_ptr(cost), _np_ptr(status), _np_ptr(iters)), "btrapz_multi_download")
         return dict(ctrl=ctrl, cost=cost, status=status, iters=iters)
 
 
@@ -416,41 +427,32 @@ class Context:
     # ---- host-pointer path (numpy in, numpy out) ------------------------------------------
     def solve_host(self, batch, shared, max_iter=0, eps=0.0, elastic=0, elastic_tol=0.0, split=0):
         B, S = batch.B, batch.S
-        seg = np.ascontiguousarray(batch.seg, dtype=np.float64)
-        init = np.ascontiguousarray(batch.init, dtype=np.float64)
-        ref_end = np.ascontiguousarray(batch.ref_end, dtype=np.float64)
-        dlb = np.ascontiguousarray(batch.dl_bounds, dtype=np.float64)
+        seg, init, ref_end, dlb = _np_f64(batch.seg), _np_f64(batch.init), _np_f64(batch.ref_end), _np_f64(batch.dl_bounds)
         assert seg.shape == (L.NUM_SEG_FIELDS, B, S)
         ctrl = np.empty((B, 12 * S)); cost = np.empty(B)
         status = np.empty(B, dtype=np.int32); iters = np.empty(B, dtype=np.int32)
         sh = CShared.from_shared(shared); opt = _options(max_iter, eps, elastic, elastic_tol, split=split)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._check(lib().btrapz_solve_batch_host(self._h, C.byref(sh), C.byref(opt), B, S, p(seg), p(init),
-                                                  p(ref_end), p(dlb), p(ctrl), p(cost), p(status), p(iters)),
-                    "btrapz_solve_batch_host")
+        self._check(lib().btrapz_solve_batch_host(self._h, C.byref(sh), C.byref(opt), B, S, _np_ptr(seg), _np_ptr(init),
+                                                  _np_ptr(ref_end), _np_ptr(dlb), _np_ptr(ctrl), _np_ptr(cost),
+                                                  _np_ptr(status), _np_ptr(iters)), "btrapz_solve_batch_host")
         return ctrl, cost, status, iters
 
     # ---- device-pointer path (torch tensors only carry the memory) --------------------------
     def solve_device(self, B, S, shared, seg, init, ref_end, dl_bounds, ctrl, cost, status, iters=None,
                      stream=None, max_iter=0, eps=0.0, elastic=0, elastic_tol=0.0, queue=0, split=0, start=0, cap_iter=0, lean=0, compact=0):
-        sh = CShared.from_shared(shared); opt = _options(max_iter, eps, elastic, elastic_tol, queue=queue, split=split, start=start, cap_iter=cap_iter, lean=lean, compact=compact)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_solve_batch_device(self._h, C.byref(sh), C.byref(opt), B, S, ptr(seg), ptr(init),
-                                                    ptr(ref_end), ptr(dl_bounds), ptr(ctrl), ptr(cost),
-                                                    ptr(status), ptr(iters), C.c_void_p(stream or 0)),
-                    "btrapz_solve_batch_device")
+        self.prepared_solve(B, S, shared, seg, init, ref_end, dl_bounds, ctrl, cost, status, iters, stream=stream,
+                            max_iter=max_iter, eps=eps, elastic=elastic, elastic_tol=elastic_tol, queue=queue, split=split,
+                            start=start, cap_iter=cap_iter, lean=lean, compact=compact)()
 
     def prepared_solve(self, B, S, shared, seg, init, ref_end, dl_bounds, ctrl, cost, status, iters=None, stream=None,
                        **options):
         """btrapz_solve_batch_device with its argument structs built ONCE: returns a function of no arguments that
         makes the call (a replanning loop or a latency measurement pays the C call, not the marshalling).  The tensors
         and `stream` must stay alive and unchanged in place; options as in solve_device."""
-        sh = CShared.from_shared(shared); opt = _options(options.pop("max_iter", 0), options.pop("eps", 0.0), options.pop("elastic", 0),
-                                                         options.pop("elastic_tol", 0.0), **options)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        sh = CShared.from_shared(shared); opt = _options(**options)
         fn, check = lib().btrapz_solve_batch_device, self._check
-        args = (self._h, C.byref(sh), C.byref(opt), B, S, ptr(seg), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl), ptr(cost),
-                ptr(status), ptr(iters), C.c_void_p(stream or 0))
+        args = (self._h, C.byref(sh), C.byref(opt), B, S, _ptr(seg), _ptr(init), _ptr(ref_end), _ptr(dl_bounds), _ptr(ctrl),
+                _ptr(cost), _ptr(status), _ptr(iters), _stream(stream))
         keep = (sh, opt, seg, init, ref_end, dl_bounds, ctrl, cost, status, iters)
 
         def call(_keep=keep):
@@ -460,24 +462,21 @@ class Context:
     def solve_ragged_device(self, B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost,
                             status, iters=None, stream=None, max_iter=0, eps=0.0, elastic=0, elastic_tol=0.0, cap_iter=0, lean=0, compact=0):
         sh = CShared.from_shared(shared); opt = _options(max_iter, eps, elastic, elastic_tol, cap_iter=cap_iter, lean=lean, compact=compact)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_solve_ragged_device(self._h, C.byref(sh), C.byref(opt), B, seg_stride, ptr(seg),
-                                                     ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds),
-                                                     ptr(ctrl), ptr(cost), ptr(status), ptr(iters),
-                                                     C.c_void_p(stream or 0)), "btrapz_solve_ragged_device")
+        self._check(lib().btrapz_solve_ragged_device(self._h, C.byref(sh), C.byref(opt), B, seg_stride, _ptr(seg),
+                                                     _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
+                                                     _ptr(ctrl), _ptr(cost), _ptr(status), _ptr(iters), _stream(stream)),
+                    "btrapz_solve_ragged_device")
 
     def solve_warm_device(self, B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
                           iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, stream=None, max_iter=0,
                           eps=0.0, hint=None, elastic=0, elastic_tol=0.0, lean=0):
         """btrapz_solve_warm_device: seg_count None = uniform batch; x0 / lam0 / lam_out optional."""
         sh = CShared.from_shared(shared); opt = _options(max_iter, eps, elastic, elastic_tol, lean=lean)
-        raw = lambda t: t.data_ptr() if t is not None else None
-        warm = CWarm(raw(x0), raw(lam0), raw(lam_out), float(mu0), float(smin), raw(hint))
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        warm = _warm(x0, lam0, lam_out, mu0, smin, hint)
         self._check(lib().btrapz_solve_warm_device(self._h, C.byref(sh), C.byref(opt), C.byref(warm), B, seg_stride,
-                                                   ptr(seg), ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds),
-                                                   ptr(ctrl), ptr(cost), ptr(status), ptr(iters),
-                                                   C.c_void_p(stream or 0)), "btrapz_solve_warm_device")
+                                                   _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
+                                                   _ptr(ctrl), _ptr(cost), _ptr(status), _ptr(iters), _stream(stream)),
+                    "btrapz_solve_warm_device")
 
     def solve_sets_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
                           iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, hint=None, stream=None,
@@ -485,17 +484,13 @@ class Context:
         """btrapz_solve_sets_device: sets = list of layout.Shared (one per parameter set), set_index = [B] int32 device
         tensor (a value outside [0, len(sets)): that candidate is not solved, status NO_CORRIDOR); seg_count None =
         uniform batch.  Warm start as in solve_warm_device (hint is accepted and ignored by the library)."""
-        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
         opt = _options(max_iter, eps, elastic, split=split, cap_iter=cap_iter, lean=lean, compact=compact)
-        raw = lambda t: t.data_ptr() if t is not None else None
         use_warm = any(t is not None for t in (x0, lam0, lam_out, hint))
-        warm = CWarm(raw(x0), raw(lam0), raw(lam_out), float(mu0), float(smin), raw(hint)) if use_warm else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_solve_sets_device(self._h, arr, len(sets), ptr(set_index), C.byref(opt),
-                                                   C.byref(warm) if warm is not None else None, B, seg_stride, ptr(seg),
-                                                   ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
-                                                   ptr(cost), ptr(status), ptr(iters), C.c_void_p(stream or 0)),
-                    "btrapz_solve_sets_device")
+        warm = C.byref(_warm(x0, lam0, lam_out, mu0, smin, hint)) if use_warm else None
+        self._check(lib().btrapz_solve_sets_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), C.byref(opt),
+                                                   warm, B, seg_stride, _ptr(seg), _ptr(seg_count), _ptr(init),
+                                                   _ptr(ref_end), _ptr(dl_bounds), _ptr(ctrl), _ptr(cost), _ptr(status),
+                                                   _ptr(iters), _stream(stream)), "btrapz_solve_sets_device")
 
     def solve_vjp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
                          ctrl_bar, cost_bar, g_seg=None, g_init=None, g_ref_end=None, g_dl_bounds=None, g_shared=None,
@@ -503,14 +498,11 @@ class Context:
         """btrapz_solve_vjp_device: gradients of a solve (elastic = 0, multipliers kept) w.r.t. its inputs.  sets = list of
         layout.Shared; set_index None = every candidate with sets[0]; seg_count None = uniform batch; ctrl_bar / cost_bar
         may be None (zero); the g_* device tensors are overwritten (None: not wanted)."""
-        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
-        raw = lambda t: t.data_ptr() if t is not None else None
-        grads = CGrads(raw(g_seg), raw(g_init), raw(g_ref_end), raw(g_dl_bounds), raw(g_shared))
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_solve_vjp_device(self._h, arr, len(sets), ptr(set_index), B, seg_stride, ptr(seg),
-                                                  ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
-                                                  ptr(lam), ptr(status), ptr(ctrl_bar), ptr(cost_bar), C.byref(grads),
-                                                  C.c_void_p(stream or 0)), "btrapz_solve_vjp_device")
+        grads = CGrads(_ptr(g_seg), _ptr(g_init), _ptr(g_ref_end), _ptr(g_dl_bounds), _ptr(g_shared))
+        self._check(lib().btrapz_solve_vjp_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), B, seg_stride,
+                                                  _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
+                                                  _ptr(ctrl), _ptr(lam), _ptr(status), _ptr(ctrl_bar), _ptr(cost_bar),
+                                                  C.byref(grads), _stream(stream)), "btrapz_solve_vjp_device")
 
     def solve_jvp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
                          T, seg_dot=None, init_dot=None, ref_end_dot=None, dl_bounds_dot=None, shared_dot=None,
@@ -518,37 +510,31 @@ class Context:
         """btrapz_solve_jvp_device: directional derivatives of a solve (elastic = 0, multipliers kept) along T tangents per
         candidate.  sets / set_index / seg_count as in solve_vjp_device; the *_dot device tensors carry a leading axis T
         (None: zero); ctrl_dot [T, B, 12 seg_stride] / cost_dot [T, B] are overwritten (either may be None)."""
-        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
-        raw = lambda t: t.data_ptr() if t is not None else None
-        tan = CTangents(raw(seg_dot), raw(init_dot), raw(ref_end_dot), raw(dl_bounds_dot), raw(shared_dot))
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_solve_jvp_device(self._h, arr, len(sets), ptr(set_index), B, seg_stride, ptr(seg),
-                                                  ptr(seg_count), ptr(init), ptr(ref_end), ptr(dl_bounds), ptr(ctrl),
-                                                  ptr(lam), ptr(status), int(T), C.byref(tan), ptr(ctrl_dot), ptr(cost_dot),
-                                                  C.c_void_p(stream or 0)), "btrapz_solve_jvp_device")
+        tan = CTangents(_ptr(seg_dot), _ptr(init_dot), _ptr(ref_end_dot), _ptr(dl_bounds_dot), _ptr(shared_dot))
+        self._check(lib().btrapz_solve_jvp_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), B, seg_stride,
+                                                  _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
+                                                  _ptr(ctrl), _ptr(lam), _ptr(status), int(T), C.byref(tan), _ptr(ctrl_dot),
+                                                  _ptr(cost_dot), _stream(stream)), "btrapz_solve_jvp_device")
 
     def traj_cost_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
                          ref_stride, a_cost, n_points=None, stream=None):
         """btrapz_traj_cost_device: a_cost [B] of the sampled trajectories of ctrl, scored with sets (list of layout.Shared;
         set_index None = every candidate with sets[0]); seg_count / status / n_points may be None; ref_stride N or 0."""
-        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_traj_cost_device(self._h, arr, len(sets), ptr(set_index), int(B), int(seg_stride), ptr(seg),
-                                                  ptr(seg_count), ptr(init), ptr(ctrl), ptr(status), int(N), ptr(s_ref),
-                                                  ptr(l_ref), int(ref_stride), ptr(a_cost), ptr(n_points),
-                                                  C.c_void_p(stream or 0)), "btrapz_traj_cost_device")
+        self._check(lib().btrapz_traj_cost_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), int(B),
+                                                  int(seg_stride), _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ctrl),
+                                                  _ptr(status), int(N), _ptr(s_ref), _ptr(l_ref), int(ref_stride),
+                                                  _ptr(a_cost), _ptr(n_points), _stream(stream)), "btrapz_traj_cost_device")
 
     def traj_cost_vjp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
                              ref_stride, a_cost_bar, ctrl_bar=None, init_bar=None, params_bar=None, s_ref_bar=None,
                              l_ref_bar=None, stream=None):
         """btrapz_traj_cost_vjp_device: the gradient device tensors (any may be None) are overwritten."""
-        arr = (CShared * max(len(sets), 1))(*[CShared.from_shared(sh) for sh in sets])
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_traj_cost_vjp_device(self._h, arr, len(sets), ptr(set_index), int(B), int(seg_stride),
-                                                      ptr(seg), ptr(seg_count), ptr(init), ptr(ctrl), ptr(status), int(N),
-                                                      ptr(s_ref), ptr(l_ref), int(ref_stride), ptr(a_cost_bar),
-                                                      ptr(ctrl_bar), ptr(init_bar), ptr(params_bar), ptr(s_ref_bar),
-                                                      ptr(l_ref_bar), C.c_void_p(stream or 0)), "btrapz_traj_cost_vjp_device")
+        self._check(lib().btrapz_traj_cost_vjp_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), int(B),
+                                                      int(seg_stride), _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ctrl),
+                                                      _ptr(status), int(N), _ptr(s_ref), _ptr(l_ref), int(ref_stride),
+                                                      _ptr(a_cost_bar), _ptr(ctrl_bar), _ptr(init_bar), _ptr(params_bar),
+                                                      _ptr(s_ref_bar), _ptr(l_ref_bar), _stream(stream)),
+                    "btrapz_traj_cost_vjp_device")
 
     def workspace_bytes(self):
         """btrapz_workspace_bytes: device memory the context holds for its launches right now."""
@@ -561,123 +547,106 @@ class Context:
     def rescue_violations_device(self, B, viol, stream=None):
         """btrapz_rescue_violations_device: viol [B][4] (position, velocity, acceleration, jerk rows) of the last solve
         with elastic != 0."""
-        self._check(lib().btrapz_rescue_violations_device(self._h, int(B), C.c_void_p(viol.data_ptr()),
-                                                          C.c_void_p(stream or 0)), "btrapz_rescue_violations_device")
+        self._check(lib().btrapz_rescue_violations_device(self._h, int(B), _ptr(viol), _stream(stream)),
+                    "btrapz_rescue_violations_device")
 
     def debug_axis_records(self, B):
         """(iters [B, 2], status [B, 2]) of the axis problems of the last batched solve."""
         it = np.zeros((B, 2), dtype=np.int32); st = np.zeros((B, 2), dtype=np.int32)
-        lib().btrapz_debug_axis_records.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        self._check(lib().btrapz_debug_axis_records(self._h, B, it.ctypes.data, st.ctypes.data), "btrapz_debug_axis_records")
+        self._check(lib().btrapz_debug_axis_records(self._h, B, _np_ptr(it), _np_ptr(st)), "btrapz_debug_axis_records")
         return it, st
 
     def debug_resume_keys(self, B):
         """keys [2, B] of the last capped solve's resume launch (0: not handed over)."""
         k = np.zeros((2, B), dtype=np.int32)
-        lib().btrapz_debug_resume_keys.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._check(lib().btrapz_debug_resume_keys(self._h, B, k.ctypes.data), "btrapz_debug_resume_keys")
+        self._check(lib().btrapz_debug_resume_keys(self._h, B, _np_ptr(k)), "btrapz_debug_resume_keys")
         return k
 
     def debug_mqm_tables(self, shared):
         sh = CShared.from_shared(shared)
         h = np.zeros(168); d = np.zeros(168)
-        self._check(lib().btrapz_debug_mqm_tables(self._h, C.byref(sh), h.ctypes.data, d.ctypes.data), "btrapz_debug_mqm_tables")
+        self._check(lib().btrapz_debug_mqm_tables(self._h, C.byref(sh), _np_ptr(h), _np_ptr(d)), "btrapz_debug_mqm_tables")
         return h, d
 
     def eval_states_device(self, B, seg_stride, seg_count, seg, ctrl, n_times, times, x, stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_eval_states_device(self._h, B, seg_stride, ptr(seg_count), ptr(seg), ptr(ctrl),
-                                                    int(n_times), ptr(times), ptr(x), C.c_void_p(stream or 0)),
+        self._check(lib().btrapz_eval_states_device(self._h, B, seg_stride, _ptr(seg_count), _ptr(seg), _ptr(ctrl),
+                                                    int(n_times), _ptr(times), _ptr(x), _stream(stream)),
                     "btrapz_eval_states_device")
 
     def eval_states_vjp_device(self, B, seg_stride, seg_count, seg, ctrl, n_times, times, x_bar, ctrl_bar=None,
                                times_bar=None, stream=None):
         """btrapz_eval_states_vjp_device: ctrl_bar [B, 12 seg_stride] and times_bar [B, n_times] (either may be None) are
         overwritten; ctrl may be None when times_bar is."""
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_eval_states_vjp_device(self._h, int(B), int(seg_stride), ptr(seg_count), ptr(seg), ptr(ctrl),
-                                                        int(n_times), ptr(times), ptr(x_bar), ptr(ctrl_bar), ptr(times_bar),
-                                                        C.c_void_p(stream or 0)), "btrapz_eval_states_vjp_device")
+        self._check(lib().btrapz_eval_states_vjp_device(self._h, int(B), int(seg_stride), _ptr(seg_count), _ptr(seg),
+                                                        _ptr(ctrl), int(n_times), _ptr(times), _ptr(x_bar), _ptr(ctrl_bar),
+                                                        _ptr(times_bar), _stream(stream)), "btrapz_eval_states_vjp_device")
 
     def sample_vjp_device(self, B, seg_stride, seg_count, delta, seg, sel, max_points, out_bar, ctrl_bar=None, init_bar=None,
                           stream=None, nsel=None):
         """btrapz_sample_vjp_device: ctrl_bar [nsel, 12 seg_stride] and init_bar [nsel, 6], one row per SELECTION (either
         may be None), are overwritten.  nsel: the length of sel unless given."""
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_sample_vjp_device(self._h, int(B), int(seg_stride), ptr(seg_count), float(delta), ptr(seg),
-                                                   int(nsel if nsel is not None else sel.numel() if sel is not None else 0), ptr(sel), int(max_points),
-                                                   ptr(out_bar), ptr(ctrl_bar), ptr(init_bar), C.c_void_p(stream or 0)),
-                    "btrapz_sample_vjp_device")
+        nsel = nsel if nsel is not None else sel.numel() if sel is not None else 0
+        self._check(lib().btrapz_sample_vjp_device(self._h, int(B), int(seg_stride), _ptr(seg_count), float(delta), _ptr(seg),
+                                                   int(nsel), _ptr(sel), int(max_points), _ptr(out_bar), _ptr(ctrl_bar),
+                                                   _ptr(init_bar), _stream(stream)), "btrapz_sample_vjp_device")
 
     def corridor_batch_device(self, variant, B, N, num_obs, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots,
                               s_ref, l_ref, seg_stride, seg, seg_count, ref_end, dl_bounds, stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         self._check(lib().btrapz_corridor_batch_device(self._h, int(variant), B, N, num_obs, float(delta),
-                                                       ptr(s_bounds), ptr(l_bounds), ptr(ds_bounds),
-                                                       ptr(dl_bounds_knots), ptr(s_ref), ptr(l_ref), seg_stride,
-                                                       ptr(seg), ptr(seg_count), ptr(ref_end), ptr(dl_bounds),
-                                                       C.c_void_p(stream or 0)), "btrapz_corridor_batch_device")
+                                                       _ptr(s_bounds), _ptr(l_bounds), _ptr(ds_bounds),
+                                                       _ptr(dl_bounds_knots), _ptr(s_ref), _ptr(l_ref), seg_stride,
+                                                       _ptr(seg), _ptr(seg_count), _ptr(ref_end), _ptr(dl_bounds),
+                                                       _stream(stream)), "btrapz_corridor_batch_device")
 
     def corridor_batch_vjp_device(self, variant, B, N, num_obs, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots,
                                   s_ref, l_ref, seg_stride, seg_bar, ref_end_bar, dl_bounds_bar, grads, stream=None):
         """btrapz_corridor_batch_vjp_device: grads = dict name -> device tensor (KNOT_GRADS; missing or None: not wanted),
         overwritten; the cotangents may be None."""
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        raw = lambda t: t.data_ptr() if t is not None else None
-        g = CKnotGrads(*[raw(grads.get(k)) for k in KNOT_GRADS]) if grads is not None else None
+        g = C.byref(CKnotGrads(*[_ptr(grads.get(k)) for k in KNOT_GRADS])) if grads is not None else None
         self._check(lib().btrapz_corridor_batch_vjp_device(self._h, int(variant), int(B), int(N), int(num_obs), float(delta),
-                                                           ptr(s_bounds), ptr(l_bounds), ptr(ds_bounds), ptr(dl_bounds_knots),
-                                                           ptr(s_ref), ptr(l_ref), int(seg_stride), ptr(seg_bar),
-                                                           ptr(ref_end_bar), ptr(dl_bounds_bar),
-                                                           C.byref(g) if g is not None else None, C.c_void_p(stream or 0)),
-                    "btrapz_corridor_batch_vjp_device")
+                                                           _ptr(s_bounds), _ptr(l_bounds), _ptr(ds_bounds),
+                                                           _ptr(dl_bounds_knots), _ptr(s_ref), _ptr(l_ref), int(seg_stride),
+                                                           _ptr(seg_bar), _ptr(ref_end_bar), _ptr(dl_bounds_bar), g,
+                                                           _stream(stream)), "btrapz_corridor_batch_vjp_device")
 
     def prism_bounds_device(self, B, P, N, road, prisms, O, s_bounds, l_bounds, n_strips, stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        self._check(lib().btrapz_prism_bounds_device(self._h, B, P, N, C.byref(road), ptr(prisms), O, ptr(s_bounds),
-                                                     ptr(l_bounds), ptr(n_strips), C.c_void_p(stream or 0)),
+        self._check(lib().btrapz_prism_bounds_device(self._h, B, P, N, C.byref(road), _ptr(prisms), O, _ptr(s_bounds),
+                                                     _ptr(l_bounds), _ptr(n_strips), _stream(stream)),
                     "btrapz_prism_bounds_device")
 
     def prism_bounds_vjp_device(self, B, P, N, road, prisms, O, s_bounds_bar, l_bounds_bar, prisms_bar, stream=None):
         """btrapz_prism_bounds_vjp_device: prisms_bar [B, P, 8] is overwritten; either cotangent may be None (zero)."""
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         self._check(lib().btrapz_prism_bounds_vjp_device(self._h, int(B), int(P), int(N), C.byref(road) if road is not None else None,
-                                                         ptr(prisms), int(O), ptr(s_bounds_bar), ptr(l_bounds_bar),
-                                                         ptr(prisms_bar), C.c_void_p(stream or 0)),
-                    "btrapz_prism_bounds_vjp_device")
+                                                         _ptr(prisms), int(O), _ptr(s_bounds_bar), _ptr(l_bounds_bar),
+                                                         _ptr(prisms_bar), _stream(stream)), "btrapz_prism_bounds_vjp_device")
 
     def prism_corridor_batch_device(self, variant, B, P, N, road, prisms, O, delta, ds_bounds, dl_bounds_knots, s_ref, l_ref,
                                     seg_stride, seg, seg_count, ref_end, dl_bounds, n_strips=None, stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_prism_corridor_batch_device(self._h, int(variant), B, P, N, C.byref(road), ptr(prisms), O,
-                                                             float(delta), ptr(ds_bounds), ptr(dl_bounds_knots), ptr(s_ref),
-                                                             ptr(l_ref), seg_stride, ptr(seg), ptr(seg_count), ptr(ref_end),
-                                                             ptr(dl_bounds), ptr(n_strips), C.c_void_p(stream or 0)),
+        self._check(lib().btrapz_prism_corridor_batch_device(self._h, int(variant), B, P, N, C.byref(road), _ptr(prisms), O,
+                                                             float(delta), _ptr(ds_bounds), _ptr(dl_bounds_knots), _ptr(s_ref),
+                                                             _ptr(l_ref), seg_stride, _ptr(seg), _ptr(seg_count), _ptr(ref_end),
+                                                             _ptr(dl_bounds), _ptr(n_strips), _stream(stream)),
                     "btrapz_prism_corridor_batch_device")
 
     def sample_ragged_device(self, B, seg_stride, seg_count, delta, seg, init, ctrl, sel, max_points, out, npoints,
                              stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(lib().btrapz_sample_ragged_device(self._h, B, seg_stride, ptr(seg_count), float(delta), ptr(seg),
-                                                      ptr(init), ptr(ctrl), int(sel.numel()), ptr(sel),
-                                                      int(max_points), ptr(out), ptr(npoints),
-                                                      C.c_void_p(stream or 0)), "btrapz_sample_ragged_device")
+        self._check(lib().btrapz_sample_ragged_device(self._h, B, seg_stride, _ptr(seg_count), float(delta), _ptr(seg),
+                                                      _ptr(init), _ptr(ctrl), int(sel.numel()), _ptr(sel),
+                                                      int(max_points), _ptr(out), _ptr(npoints), _stream(stream)),
+                    "btrapz_sample_ragged_device")
 
     def argmin_device(self, B, group, index_base, cost, best_idx, best_cost, stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        self._check(lib().btrapz_argmin_device(self._h, B, group, int(index_base), ptr(cost), ptr(best_idx),
-                                               ptr(best_cost), C.c_void_p(stream or 0)), "btrapz_argmin_device")
+        self._check(lib().btrapz_argmin_device(self._h, B, group, int(index_base), _ptr(cost), _ptr(best_idx),
+                                               _ptr(best_cost), _stream(stream)), "btrapz_argmin_device")
 
     def argmin_pairs_device(self, world, n, pairs, best_cost, best_idx, stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        self._check(lib().btrapz_argmin_pairs_device(self._h, int(world), int(n), ptr(pairs), ptr(best_cost), ptr(best_idx),
-                                                     C.c_void_p(stream or 0)), "btrapz_argmin_pairs_device")
+        self._check(lib().btrapz_argmin_pairs_device(self._h, int(world), int(n), _ptr(pairs), _ptr(best_cost), _ptr(best_idx),
+                                                     _stream(stream)), "btrapz_argmin_pairs_device")
 
     def sample_device(self, B, S, delta, seg, init, ctrl, sel, max_points, out, npoints, stream=None):
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        self._check(lib().btrapz_sample_device(self._h, B, S, float(delta), ptr(seg), ptr(init), ptr(ctrl),
-                                               int(sel.numel()), ptr(sel), int(max_points), ptr(out), ptr(npoints),
-                                               C.c_void_p(stream or 0)), "btrapz_sample_device")
+        self._check(lib().btrapz_sample_device(self._h, B, S, float(delta), _ptr(seg), _ptr(init), _ptr(ctrl),
+                                               int(sel.numel()), _ptr(sel), int(max_points), _ptr(out), _ptr(npoints),
+                                               _stream(stream)), "btrapz_sample_device")
 
 
 def find_traj_native(variant, params, input_path=None, output_path=None):
@@ -702,8 +671,7 @@ class TrajCall:
     def __init__(self, variant, params, kb, b=0, cap=None):
         self.variant = int(variant)
         self.cp = params if isinstance(params, CParams) else CParams(*params)
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        self._arrs = [f(kb.s_bounds[b]), f(kb.l_bounds[b]), f(kb.ds_bounds[b]), f(kb.dl_bounds[b]), f(kb.s_ref[b]), f(kb.l_ref[b])]
+        self._arrs = [_np_f64(a[b]) for a in (kb.s_bounds, kb.l_bounds, kb.ds_bounds, kb.dl_bounds, kb.s_ref, kb.l_ref)]
         h = kb.header
         self.ti = CTrajInput(int(kb.N), int(kb.num_obs), float(kb.delta), (C.c_double * 3)(*kb.init[b, :3]),
                              (C.c_double * 3)(*kb.init[b, 3:]), float(h["ds_ref"]), float(h["dl_ref"]),
@@ -735,18 +703,18 @@ def find_traj_mem(variant, params, kb, b=0, cap=None):
 def prism_bounds_vjp_host(prisms, N, O, s_bounds_bar=None, l_bounds_bar=None, road=None):
     """btrapz_prism_bounds_vjp_host(): the backward pass of the prism stage on the host (no GPU).  prisms [B, P, 8];
     s_bounds_bar, l_bounds_bar [B, O, N, 2] (either may be None: zero).  Returns prisms_bar [B, P, 8]."""
-    prisms = np.ascontiguousarray(prisms, dtype=np.float64)
+    prisms = _np_f64(prisms)
     if prisms.ndim != 3 or prisms.shape[2] != 8:
         raise ValueError("prisms must be [B, P, 8]")
     B, P = prisms.shape[0], prisms.shape[1]
-    bars = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (s_bounds_bar, l_bounds_bar)]
+    bars = [_np_f64(s_bounds_bar), _np_f64(l_bounds_bar)]
     for a in bars:
         if a is not None and a.shape != (B, int(O), int(N), 2):
             raise ValueError("a cotangent must be [B, O, N, 2]")
     out = np.full((B, P, 8), np.nan)
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
     road = CRoad.reference() if road is None else road
-    rc = lib().btrapz_prism_bounds_vjp_host(B, P, int(N), C.byref(road), p(prisms), int(O), p(bars[0]), p(bars[1]), p(out))
+    rc = lib().btrapz_prism_bounds_vjp_host(B, P, int(N), C.byref(road), _np_ptr(prisms), int(O), _np_ptr(bars[0]),
+                                            _np_ptr(bars[1]), _np_ptr(out))
     if rc != 0:
         raise BtrapzError("btrapz_prism_bounds_vjp_host -> %d (invalid argument)" % rc)
     return out
@@ -758,19 +726,18 @@ def corridor_vjp_host(variant, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_k
     s_bounds, l_bounds [num_obs, N, 2]; ds_bounds, dl_bounds_knots [N, 2]; s_ref, l_ref [N]; seg_bar
     [NUM_SEG_FIELDS, seg_stride], ref_end_bar [2], dl_bounds_bar [10] (any may be None).  Returns (dict of the wanted
     gradient arrays, the forward's seg_count)."""
-    f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-    sb, lb, ds, dl, sr, lr = (f(a) for a in (s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref))
+    ins = [_np_f64(a) for a in (s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref)]
+    sb = ins[0]
     num_obs, N = (sb.shape[0], sb.shape[1]) if sb is not None else (0, 0)
-    bars = [f(seg_bar), f(ref_end_bar), f(dl_bounds_bar)]
+    bars = [_np_f64(seg_bar), _np_f64(ref_end_bar), _np_f64(dl_bounds_bar)]
     if bars[0] is not None:
         assert bars[0].shape == (L.NUM_SEG_FIELDS, seg_stride)
     shapes = dict(s_bounds=(num_obs, N, 2), l_bounds=(num_obs, N, 2), ds_bounds=(N, 2), dl_bounds_knots=(N, 2), s_ref=(N,), l_ref=(N,))
     out = {k: np.full(shapes[k], np.nan) for k in want}
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-    g = CKnotGrads(*[out[k].ctypes.data if k in out else None for k in KNOT_GRADS])
+    g = CKnotGrads(*[_np_ptr(out.get(k)) for k in KNOT_GRADS])
     count = C.c_int(-2)
-    rc = lib().btrapz_corridor_vjp_host(int(variant), int(N), int(num_obs), float(delta), p(sb), p(lb), p(ds), p(dl), p(sr), p(lr),
-                                        int(seg_stride), p(bars[0]), p(bars[1]), p(bars[2]), C.byref(g), C.byref(count))
+    rc = lib().btrapz_corridor_vjp_host(int(variant), int(N), int(num_obs), float(delta), *[_np_ptr(a) for a in ins],
+                                        int(seg_stride), *[_np_ptr(a) for a in bars], C.byref(g), C.byref(count))
     if rc != 0:
         raise BtrapzError("btrapz_corridor_vjp_host -> %d (invalid argument)" % rc)
     return out, count.value

@@ -4,20 +4,41 @@ import numpy as np
 import torch
 
 from . import layout as L
-from .native import Context
+from .native import Context, CRoad
 
 
 class DeviceBatch:
-    """A candidate batch resident in HBM (field-major SoA, see layout.py)."""
+    """A candidate batch resident in HBM (field-major SoA, see layout.py): B candidates of S segment slots each.
+    seg_count None: a uniform batch, every candidate has S segments; an int32 [B] device tensor: a ragged batch of
+    stride S.  Arrays a call does not read may be None."""
 
     def __init__(self, batch, device):
-        self.B, self.S = batch.B, batch.S
         f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+        self.B, self.S, self.seg_count = batch.B, batch.S, None
         self.seg, self.init, self.ref_end, self.dl_bounds = f(batch.seg), f(batch.init), f(batch.ref_end), f(batch.dl_bounds)
+
+    @classmethod
+    def from_tensors(cls, seg, init=None, ref_end=None, dl_bounds=None, seg_count=None, B=None, S=None):
+        """The record of device tensors that are there already; B and S default to seg's extents [NUM_SEG_FIELDS, B, S]."""
+        r = cls.__new__(cls)
+        r.B, r.S = seg.shape[1] if B is None else B, seg.shape[2] if S is None else S
+        r.seg, r.init, r.ref_end, r.dl_bounds, r.seg_count = seg, init, ref_end, dl_bounds, seg_count
+        return r
+
+
+def _sets_of(shared_or_sets):
+    """A layout.Shared, or a list / tuple of them -> the list of parameter sets."""
+    return list(shared_or_sets) if isinstance(shared_or_sets, (list, tuple)) else [shared_or_sets]
+
+
+def _check_index(t, B):
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
 
 
 class BatchSolver:
-    """Solves DeviceBatches on one GPU; outputs stay on the device."""
+    """Solves DeviceBatches on one GPU; outputs stay on the device.  Wherever a method takes a batch it takes either
+    shape of one: a DeviceBatch, or a ragged record dict (B, seg_stride, seg, seg_count, init, ref_end, dl_bounds; as
+    corridor_batch returns it; seg_count None or absent: uniform)."""
 
     def __init__(self, device_index=0):
         if not torch.cuda.is_available():
@@ -29,16 +50,79 @@ class BatchSolver:
     def upload(self, batch):
         return DeviceBatch(batch, self.device)
 
+    # ---- the one way to do each repeated thing ------------------------------------------------
+    @staticmethod
+    def _record(x):
+        """Either shape of a batch -> DeviceBatch (names B, S, seg_count, seg, init, ref_end, dl_bounds; missing: None)."""
+        if isinstance(x, DeviceBatch):
+            return x
+        if isinstance(x, dict):
+            return DeviceBatch.from_tensors(x["seg"], x.get("init"), x.get("ref_end"), x.get("dl_bounds"), x.get("seg_count"),
+                                            B=x["B"], S=x["seg_stride"])
+        g = lambda k: getattr(x, k, None)     # (an object with the DeviceBatch attributes a call reads)
+        return DeviceBatch.from_tensors(x.seg, g("init"), g("ref_end"), g("dl_bounds"), g("seg_count"), B=x.B, S=x.S)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _empty(self, *shape, dtype=torch.float64):
+        return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def _zeros(self, *shape, dtype=torch.float64):
+        return torch.zeros(shape, dtype=dtype, device=self.device)
+
+    def _upload(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)
+
+    def _f64(self, t, detach=False):
+        """A tensor as contiguous float64 on this device (itself when it is that already); None -> None."""
+        if t is None:
+            return None
+        return (t.detach() if detach else t).to(self.device, dtype=torch.float64).contiguous()
+
+    def new_result(self, B, S, zero_ctrl=False):
+        """A fresh result dict of device tensors: ctrl [B, 12 S], cost, status, iters [B].  zero_ctrl: what a ragged solve
+        needs and a uniform one does not -- the slots beyond a candidate's segment count are not written and must read 0."""
+        return dict(ctrl=(self._zeros if zero_ctrl else self._empty)(B, 12 * S), cost=self._empty(B),
+                    status=self._empty(B, dtype=torch.int32), iters=self._empty(B, dtype=torch.int32))
+
     def _buffers(self, B, S):
+        """The result dict uniform solves of this shape share: a loop of solves allocates nothing."""
         key = (B, S)
         if key not in self._out:
-            d = self.device
-            self._out[key] = dict(ctrl=torch.empty((B, 12 * S), dtype=torch.float64, device=d),
-                                  cost=torch.empty(B, dtype=torch.float64, device=d),
-                                  status=torch.empty(B, dtype=torch.int32, device=d),
-                                  iters=torch.empty(B, dtype=torch.int32, device=d))
+            self._out[key] = self.new_result(B, S)
         return self._out[key]
 
+    def _out_of(self, r, out):
+        """The caller's `out`; else the shared buffers of a uniform batch, a fresh zeroed result for a ragged one."""
+        if out is not None:
+            return out
+        return self._buffers(r.B, r.S) if r.seg_count is None else self.new_result(r.B, r.S, zero_ctrl=True)
+
+    def _ragged_record(self, B, seg_stride, init, **more):
+        """The dict the corridor stages fill: a ragged batch record, zeroed (a candidate's unused slots read 0)."""
+        return dict(B=B, seg_stride=seg_stride, seg=self._zeros(L.NUM_SEG_FIELDS, B, seg_stride),
+                    seg_count=self._zeros(B, dtype=torch.int32), init=init, ref_end=self._zeros(B, 2),
+                    dl_bounds=self._zeros(B, 10), **more)
+
+    def _warm(self, r, warm, keep_multipliers, o):
+        """The btrapz_warm arguments of a solve of record r, shapes checked, and the result dict, which gains "lam" when
+        the multipliers are kept."""
+        warm = warm or {}
+        x0, lam0 = warm.get("x0"), warm.get("lam")
+        if x0 is not None:
+            assert x0.dtype == torch.float64 and x0.is_contiguous() and tuple(x0.shape) == (r.B, 2, r.S, 3)
+        if lam0 is not None:
+            assert lam0.dtype == torch.float64 and lam0.is_contiguous() and tuple(lam0.shape) == (2, 36, r.B, r.S)
+        lam_out = None
+        if keep_multipliers:
+            # in place when a previous solve's array is passed in (allowed: include/btrapz_hip.h, btrapz_warm)
+            lam_out = lam0 if lam0 is not None else self._empty(2, 36, r.B, r.S)
+            o = dict(o); o["lam"] = lam_out
+        return dict(x0=x0, lam0=lam0, lam_out=lam_out, mu0=warm.get("mu0", 0.0), smin=warm.get("smin", 0.0),
+                    hint=warm.get("hint")), o
+
+    # ---- solves -----------------------------------------------------------------------------
     def solve(self, dbatch, shared, max_iter=0, eps=0.0, out=None, warm=None, keep_multipliers=False, elastic=0,
               elastic_tol=0.0, queue=0, split=0, start=0, cap_iter=0, lean=0, compact=0):
         """Launches the solve on torch's current stream; returns dict of device tensors.
@@ -49,70 +133,84 @@ class BatchSolver:
         adds this solve's multipliers to the result as "lam".  elastic: btrapz_options.elastic (0 off, 1 rescue pass
         over stalled candidates, 2 elastic rows for every candidate).  split: btrapz_options.split (0 automatic: the
         one-candidate-per-wavefront form for batches that leave SIMDs idle; 1 always where it applies; -1 never).  lean:
-        btrapz_options.lean (the two-wavefronts-per-SIMD form of cold solves: 0 automatic, 1 where it applies, -1 never)."""
-        o = out if out is not None else self._buffers(dbatch.B, dbatch.S)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        btrapz_options.lean (the two-wavefronts-per-SIMD form of cold solves: 0 automatic, 1 where it applies, -1 never).
+        A ragged record is taken with warm or keep_multipliers (btrapz_solve_warm_device); its cold solve is solve_ragged."""
+        r = self._record(dbatch)
         if warm is None and not keep_multipliers:
-            self.ctx.solve_device(dbatch.B, dbatch.S, shared, dbatch.seg, dbatch.init, dbatch.ref_end,
-                                  dbatch.dl_bounds, o["ctrl"], o["cost"], o["status"], o["iters"], stream=stream,
-                                  max_iter=max_iter, eps=eps, elastic=elastic, elastic_tol=elastic_tol, queue=queue,
-                                  split=split, start=start, cap_iter=cap_iter, lean=lean, compact=compact)
+            if r.seg_count is not None:
+                raise ValueError("solve: the cold solve of a ragged record is solve_ragged")
+            o = self._out_of(r, out)
+            self.ctx.solve_device(r.B, r.S, shared, r.seg, r.init, r.ref_end, r.dl_bounds, o["ctrl"], o["cost"],
+                                  o["status"], o["iters"], stream=self._stream(), max_iter=max_iter, eps=eps,
+                                  elastic=elastic, elastic_tol=elastic_tol, queue=queue, split=split, start=start,
+                                  cap_iter=cap_iter, lean=lean, compact=compact)
             return o
-        warm = warm or {}
-        x0, lam0, hint = warm.get("x0"), warm.get("lam"), warm.get("hint")
-        if hint is not None:
-            assert hint.dtype == torch.int32 and hint.is_contiguous() and hint.numel() == dbatch.B
-        if x0 is not None:
-            assert x0.dtype == torch.float64 and x0.is_contiguous() and tuple(x0.shape) == (dbatch.B, 2, dbatch.S, 3)
-        if lam0 is not None:
-            assert lam0.dtype == torch.float64 and lam0.is_contiguous() and tuple(lam0.shape) == (2, 36, dbatch.B, dbatch.S)
-        lam_out = None
-        if keep_multipliers:
-            # in place when a previous solve's array is passed in (allowed: include/btrapz_hip.h, btrapz_warm)
-            lam_out = lam0 if lam0 is not None else torch.empty((2, 36, dbatch.B, dbatch.S), dtype=torch.float64,
-                                                                device=self.device)
-            o = dict(o); o["lam"] = lam_out
-        self.ctx.solve_warm_device(dbatch.B, dbatch.S, shared, dbatch.seg, None, dbatch.init, dbatch.ref_end,
-                                   dbatch.dl_bounds, o["ctrl"], o["cost"], o["status"], o["iters"], x0=x0, lam0=lam0,
-                                   lam_out=lam_out, mu0=warm.get("mu0", 0.0), smin=warm.get("smin", 0.0),
-                                   stream=stream, max_iter=max_iter, eps=eps, hint=hint, elastic=elastic,
-                                   elastic_tol=elastic_tol, lean=lean)
+        w, o = self._warm(r, warm, keep_multipliers, self._out_of(r, out))
+        if w["hint"] is not None:
+            _check_index(w["hint"], r.B)
+        self.ctx.solve_warm_device(r.B, r.S, shared, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, o["ctrl"],
+                                   o["cost"], o["status"], o["iters"], stream=self._stream(), max_iter=max_iter, eps=eps,
+                                   elastic=elastic, elastic_tol=elastic_tol, lean=lean, **w)
         return o
 
     def prepare(self, dbatch, shared, out=None, **options):
         """solve(dbatch, shared, **options) prepared once: returns (call, out) where call() launches the solve on the
         stream that is current NOW and `out` is the dict of device tensors it fills (cold solves only)."""
-        o = out if out is not None else self._buffers(dbatch.B, dbatch.S)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        call = self.ctx.prepared_solve(dbatch.B, dbatch.S, shared, dbatch.seg, dbatch.init, dbatch.ref_end, dbatch.dl_bounds,
-                                       o["ctrl"], o["cost"], o["status"], o["iters"], stream=stream, **options)
+        r = self._record(dbatch)
+        o = out if out is not None else self._buffers(r.B, r.S)
+        call = self.ctx.prepared_solve(r.B, r.S, shared, r.seg, r.init, r.ref_end, r.dl_bounds, o["ctrl"], o["cost"],
+                                       o["status"], o["iters"], stream=self._stream(), **options)
         return call, o
+
+    def solve_ragged(self, rec, shared, max_iter=0, eps=0.0, elastic=0, elastic_tol=0.0, cap_iter=0, lean=0, compact=0):
+        """Solve a ragged batch record (from corridor_batch); outputs stay on the device.  cap_iter:
+        btrapz_options.cap_iter (0 automatic, -1 one launch, n two launches with hand-over after n iterations)."""
+        r = self._record(rec)
+        o = self.new_result(r.B, r.S, zero_ctrl=True)
+        self.ctx.solve_ragged_device(r.B, r.S, shared, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, o["ctrl"],
+                                     o["cost"], o["status"], o["iters"], stream=self._stream(), max_iter=max_iter, eps=eps,
+                                     elastic=elastic, elastic_tol=elastic_tol, cap_iter=cap_iter, lean=lean, compact=compact)
+        return o
+
+    def _sets_call(self, r, sets, set_index, o, warm, keep_multipliers, options):
+        _check_index(set_index, r.B)
+        w, o = self._warm(r, warm, keep_multipliers, o)
+        self.ctx.solve_sets_device(r.B, r.S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, o["ctrl"],
+                                   o["cost"], o["status"], o["iters"], stream=self._stream(), **w, **options)
+        return o
+
+    def solve_sets(self, dbatch, sets, set_index, warm=None, keep_multipliers=False, out=None, **options):
+        """A parameter set per candidate (btrapz_solve_sets_device): sets is a list of layout.Shared, set_index an int32
+        device tensor [B] naming each candidate's set (outside [0, len(sets)): not solved, status NO_CORRIDOR, cost
+        +inf).  warm / keep_multipliers as in solve(); options: max_iter, eps, lean (0 / 1 / -1), cap_iter and compact
+        (0 or -1: the sets path runs one launch without the pre-pass).  Returns the dict of device tensors."""
+        r = self._record(dbatch)
+        return self._sets_call(r, sets, set_index, self._out_of(r, out), warm, keep_multipliers, options)
+
+    def solve_sets_ragged(self, rec, sets, set_index, warm=None, keep_multipliers=False, **options):
+        """solve_sets for a ragged batch record (from corridor_batch): candidates of up to 64 segments."""
+        r = self._record(rec)
+        return self._sets_call(r, sets, set_index, self.new_result(r.B, r.S, zero_ctrl=True), warm, keep_multipliers, options)
 
     def eval_states(self, dbatch, ctrl, times):
         """(p, v, a) of every candidate's solved trajectory at times[b][j] (seconds from the start of its
         horizon) -> [B, 2, n_times, 3]; the x0 of a warm start."""
-        times = times.to(self.device, dtype=torch.float64).contiguous()
+        r = self._record(dbatch)
+        times = self._f64(times)
         n = times.shape[1]
-        x = torch.empty((dbatch.B, 2, n, 3), dtype=torch.float64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx.eval_states_device(dbatch.B, dbatch.S, None, dbatch.seg, ctrl, n, times, x, stream=stream)
+        x = self._empty(r.B, 2, n, 3)
+        self.ctx.eval_states_device(r.B, r.S, r.seg_count, r.seg, ctrl, n, times, x, stream=self._stream())
         return x
 
+    # ---- the stages in front of the solve -----------------------------------------------------
     def corridor_batch(self, kb, variant, seg_stride=16):
         """Device corridor stage on a spectral_amd.knots.KnotBatch -> dict of device tensors forming a ragged
         batch record (seg, seg_count, init, ref_end, dl_bounds)."""
-        d = self.device
-        f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(d)
-        B = kb.B
-        rec = dict(B=B, seg_stride=seg_stride,
-                   seg=torch.zeros((L.NUM_SEG_FIELDS, B, seg_stride), dtype=torch.float64, device=d),
-                   seg_count=torch.zeros(B, dtype=torch.int32, device=d), init=f(kb.init),
-                   ref_end=torch.zeros((B, 2), dtype=torch.float64, device=d),
-                   dl_bounds=torch.zeros((B, 10), dtype=torch.float64, device=d))
-        ins = [f(kb.s_bounds), f(kb.l_bounds), f(kb.ds_bounds), f(kb.dl_bounds), f(kb.s_ref), f(kb.l_ref)]
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.corridor_batch_device(variant, B, kb.N, kb.num_obs, kb.delta, *ins, seg_stride, rec["seg"],
-                                       rec["seg_count"], rec["ref_end"], rec["dl_bounds"], stream=stream)
+        up = self._upload
+        rec = self._ragged_record(kb.B, seg_stride, up(kb.init))
+        ins = [up(kb.s_bounds), up(kb.l_bounds), up(kb.ds_bounds), up(kb.dl_bounds), up(kb.s_ref), up(kb.l_ref)]
+        self.ctx.corridor_batch_device(variant, kb.B, kb.N, kb.num_obs, kb.delta, *ins, seg_stride, rec["seg"],
+                                       rec["seg_count"], rec["ref_end"], rec["dl_bounds"], stream=self._stream())
         rec["_inputs"] = ins  # keep the knot arrays alive until the launch has run
         return rec
 
@@ -126,19 +224,16 @@ class BatchSolver:
         all).  seg_stride: the forward call's (a corridor of more segments has seg_count -1 there and zeros here); it may be
         left out with a seg_bar, whose last extent it is, and is required without one.  Returns a dict of the arrays named
         in `want`, shaped like the inputs."""
-        d = self.device
         if hasattr(kb_or_tensors, "s_bounds"):
-            kb = kb_or_tensors
-            f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(d)
-            ins = [f(kb.s_bounds), f(kb.l_bounds), f(kb.ds_bounds), f(kb.dl_bounds), f(kb.s_ref), f(kb.l_ref)]
+            kb, up = kb_or_tensors, self._upload
+            ins = [up(kb.s_bounds), up(kb.l_bounds), up(kb.ds_bounds), up(kb.dl_bounds), up(kb.s_ref), up(kb.l_ref)]
             delta = kb.delta if delta is None else delta
         else:
-            ins = [t.detach().to(d, dtype=torch.float64).contiguous() for t in kb_or_tensors]
+            ins = [self._f64(t, detach=True) for t in kb_or_tensors]
             if delta is None:
                 raise ValueError("delta is needed with tensors")
         B, O, N = ins[0].shape[0], ins[0].shape[1], ins[0].shape[2]
-        c = lambda t: None if t is None else t.detach().to(d, dtype=torch.float64).contiguous()
-        seg_bar, ref_end_bar, dl_bounds_bar = c(seg_bar), c(ref_end_bar), c(dl_bounds_bar)
+        seg_bar, ref_end_bar, dl_bounds_bar = (self._f64(t, detach=True) for t in (seg_bar, ref_end_bar, dl_bounds_bar))
         if seg_bar is None and seg_stride is None:
             raise ValueError("seg_stride is needed without a seg_bar")
         if seg_bar is not None and seg_stride is not None and int(seg_stride) != seg_bar.shape[2]:
@@ -146,23 +241,18 @@ class BatchSolver:
         seg_stride = seg_bar.shape[2] if seg_bar is not None else int(seg_stride)
         like = dict(s_bounds=ins[0], l_bounds=ins[1], ds_bounds=ins[2], dl_bounds_knots=ins[3], s_ref=ins[4], l_ref=ins[5])
         grads = {k: torch.empty_like(like[k]) for k in want}
-        stream = torch.cuda.current_stream(d).cuda_stream
         self.ctx.corridor_batch_vjp_device(variant, B, N, O, delta, *ins, seg_stride, seg_bar, ref_end_bar, dl_bounds_bar,
-                                           grads, stream=stream)
+                                           grads, stream=self._stream())
         grads["_inputs"] = (ins, seg_bar, ref_end_bar, dl_bounds_bar)   # alive until the launch has run
         return grads
 
     def prism_bounds(self, prisms, N, O, road=None):
         """Obstacle prisms [B, P, 8] (s0, l0, t0, vel_s, vel_l, T, active, -) -> per-knot bounds of the lateral strips
         (btrapz_prism_bounds_device): s_bounds, l_bounds [B, O, N, 2] and n_strips [B], on the device."""
-        from .native import CRoad
-        d = self.device
-        prisms = prisms.to(d, dtype=torch.float64).contiguous()
+        prisms = self._f64(prisms)
         B, P = prisms.shape[0], prisms.shape[1]
-        sb = torch.empty((B, O, N, 2), dtype=torch.float64, device=d); lb = torch.empty_like(sb)
-        n = torch.empty(B, dtype=torch.int32, device=d)
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.prism_bounds_device(B, P, N, road or CRoad.reference(), prisms, O, sb, lb, n, stream=stream)
+        sb, lb, n = self._empty(B, O, N, 2), self._empty(B, O, N, 2), self._empty(B, dtype=torch.int32)
+        self.ctx.prism_bounds_device(B, P, N, road or CRoad.reference(), prisms, O, sb, lb, n, stream=self._stream())
         return sb, lb, n
 
     def prism_bounds_vjp(self, prisms, N, O, s_bounds_bar, l_bounds_bar, road=None):
@@ -170,36 +260,25 @@ class BatchSolver:
         s_bounds_bar, l_bounds_bar [B, O, N, 2] (either may be None, not both) -> prisms_bar [B, P, 8]: s0, l0, t0, vel_s,
         vel_l, T, then two zeros.  The stage's decisions are frozen and the two-decimal rounding of the faces counts as the
         identity (include/btrapz_hip.h lists the rules); a scene with more than O strips gets zeros."""
-        from .native import CRoad
-        d = self.device
-        prisms = prisms.detach().to(d, dtype=torch.float64).contiguous()
+        prisms = self._f64(prisms, detach=True)
         B, P = prisms.shape[0], prisms.shape[1]
-        c = lambda t: None if t is None else t.detach().to(d, dtype=torch.float64).contiguous()
-        sbar, lbar = c(s_bounds_bar), c(l_bounds_bar)
+        sbar, lbar = self._f64(s_bounds_bar, detach=True), self._f64(l_bounds_bar, detach=True)
         for t in (sbar, lbar):
             if t is not None and tuple(t.shape) != (B, int(O), int(N), 2):
                 raise ValueError("a cotangent must be [B, O, N, 2] = %s, not %s" % ((B, O, N, 2), tuple(t.shape)))
-        out = torch.empty((B, P, 8), dtype=torch.float64, device=d)
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.prism_bounds_vjp_device(B, P, N, road or CRoad.reference(), prisms, O, sbar, lbar, out, stream=stream)
+        out = self._empty(B, P, 8)
+        self.ctx.prism_bounds_vjp_device(B, P, N, road or CRoad.reference(), prisms, O, sbar, lbar, out, stream=self._stream())
         return out
 
     def corridor_batch_tensors(self, variant, N, delta, s_bounds, l_bounds, ds_bounds, dl_bounds, s_ref, l_ref, init,
                                seg_stride=16):
         """corridor_batch on device tensors (e.g. the output of prism_bounds): s_bounds, l_bounds [B, O, N, 2],
         ds_bounds, dl_bounds [B, N, 2], s_ref, l_ref [B, N], init [B, 6]."""
-        d = self.device
         B, O = s_bounds.shape[0], s_bounds.shape[1]
-        c = lambda t: t.to(d, dtype=torch.float64).contiguous()
-        ins = [c(s_bounds), c(l_bounds), c(ds_bounds), c(dl_bounds), c(s_ref), c(l_ref)]
-        rec = dict(B=B, seg_stride=seg_stride,
-                   seg=torch.zeros((L.NUM_SEG_FIELDS, B, seg_stride), dtype=torch.float64, device=d),
-                   seg_count=torch.zeros(B, dtype=torch.int32, device=d), init=c(init),
-                   ref_end=torch.zeros((B, 2), dtype=torch.float64, device=d),
-                   dl_bounds=torch.zeros((B, 10), dtype=torch.float64, device=d))
-        stream = torch.cuda.current_stream(d).cuda_stream
+        ins = [self._f64(t) for t in (s_bounds, l_bounds, ds_bounds, dl_bounds, s_ref, l_ref)]
+        rec = self._ragged_record(B, seg_stride, self._f64(init))
         self.ctx.corridor_batch_device(variant, B, N, O, delta, *ins, seg_stride, rec["seg"], rec["seg_count"],
-                                       rec["ref_end"], rec["dl_bounds"], stream=stream)
+                                       rec["ref_end"], rec["dl_bounds"], stream=self._stream())
         rec["_inputs"] = ins
         return rec
 
@@ -207,76 +286,23 @@ class BatchSolver:
                              road=None):
         """prism_bounds + corridor_batch_tensors in one launch (btrapz_prism_corridor_batch_device): the strips are
         evaluated inside the corridor kernel instead of written to memory.  Same record, plus rec["n_strips"]."""
-        from .native import CRoad
-        d = self.device
-        c = lambda t: t.to(d, dtype=torch.float64).contiguous()
-        prisms = c(prisms)
-        B, P = prisms.shape[0], prisms.shape[1]
-        ins = [prisms, c(ds_bounds), c(dl_bounds), c(s_ref), c(l_ref)]
-        rec = dict(B=B, seg_stride=seg_stride,
-                   seg=torch.zeros((L.NUM_SEG_FIELDS, B, seg_stride), dtype=torch.float64, device=d),
-                   seg_count=torch.zeros(B, dtype=torch.int32, device=d), init=c(init),
-                   ref_end=torch.zeros((B, 2), dtype=torch.float64, device=d),
-                   dl_bounds=torch.zeros((B, 10), dtype=torch.float64, device=d),
-                   n_strips=torch.empty(B, dtype=torch.int32, device=d))
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.prism_corridor_batch_device(variant, B, P, N, road or CRoad.reference(), prisms, O, delta, *ins[1:],
+        ins = [self._f64(t) for t in (prisms, ds_bounds, dl_bounds, s_ref, l_ref)]
+        B, P = ins[0].shape[0], ins[0].shape[1]
+        rec = self._ragged_record(B, seg_stride, self._f64(init), n_strips=self._empty(B, dtype=torch.int32))
+        self.ctx.prism_corridor_batch_device(variant, B, P, N, road or CRoad.reference(), ins[0], O, delta, *ins[1:],
                                              seg_stride, rec["seg"], rec["seg_count"], rec["ref_end"], rec["dl_bounds"],
-                                             rec["n_strips"], stream=stream)
+                                             rec["n_strips"], stream=self._stream())
         rec["_inputs"] = ins
         return rec
 
-    def solve_ragged(self, rec, shared, max_iter=0, eps=0.0, elastic=0, elastic_tol=0.0, cap_iter=0, lean=0, compact=0):
-        """Solve a ragged batch record (from corridor_batch); outputs stay on the device.  cap_iter:
-        btrapz_options.cap_iter (0 automatic, -1 one launch, n two launches with hand-over after n iterations)."""
-        d = self.device
-        B, st = rec["B"], rec["seg_stride"]
-        o = dict(ctrl=torch.zeros((B, 12 * st), dtype=torch.float64, device=d),
-                 cost=torch.empty(B, dtype=torch.float64, device=d),
-                 status=torch.empty(B, dtype=torch.int32, device=d), iters=torch.empty(B, dtype=torch.int32, device=d))
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.solve_ragged_device(B, st, shared, rec["seg"], rec["seg_count"], rec["init"], rec["ref_end"],
-                                     rec["dl_bounds"], o["ctrl"], o["cost"], o["status"], o["iters"], stream=stream,
-                                     max_iter=max_iter, eps=eps, elastic=elastic, elastic_tol=elastic_tol, cap_iter=cap_iter, lean=lean, compact=compact)
-        return o
-
-    def _sets_call(self, B, S, sets, set_index, rec, seg_count, o, warm, keep_multipliers, options):
-        assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
-        warm = warm or {}
-        x0, lam0 = warm.get("x0"), warm.get("lam")
-        if x0 is not None:
-            assert x0.dtype == torch.float64 and x0.is_contiguous() and tuple(x0.shape) == (B, 2, S, 3)
-        if lam0 is not None:
-            assert lam0.dtype == torch.float64 and lam0.is_contiguous() and tuple(lam0.shape) == (2, 36, B, S)
-        lam_out = None
-        if keep_multipliers:
-            lam_out = lam0 if lam0 is not None else torch.empty((2, 36, B, S), dtype=torch.float64, device=self.device)
-            o = dict(o); o["lam"] = lam_out
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx.solve_sets_device(B, S, sets, set_index, rec.seg if seg_count is None else rec["seg"], seg_count,
-                                   rec.init if seg_count is None else rec["init"],
-                                   rec.ref_end if seg_count is None else rec["ref_end"],
-                                   rec.dl_bounds if seg_count is None else rec["dl_bounds"], o["ctrl"], o["cost"],
-                                   o["status"], o["iters"], x0=x0, lam0=lam0, lam_out=lam_out, mu0=warm.get("mu0", 0.0),
-                                   smin=warm.get("smin", 0.0), hint=warm.get("hint"), stream=stream, **options)
-        return o
-
-    def solve_sets(self, dbatch, sets, set_index, warm=None, keep_multipliers=False, out=None, **options):
-        """A parameter set per candidate (btrapz_solve_sets_device): sets is a list of layout.Shared, set_index an int32
-        device tensor [B] naming each candidate's set (outside [0, len(sets)): not solved, status NO_CORRIDOR, cost
-        +inf).  warm / keep_multipliers as in solve(); options: max_iter, eps, lean (0 / 1 / -1), cap_iter and compact
-        (0 or -1: the sets path runs one launch without the pre-pass).  Returns the dict of device tensors."""
-        o = out if out is not None else self._buffers(dbatch.B, dbatch.S)
-        return self._sets_call(dbatch.B, dbatch.S, sets, set_index, dbatch, None, o, warm, keep_multipliers, options)
-
-    def solve_sets_ragged(self, rec, sets, set_index, warm=None, keep_multipliers=False, **options):
-        """solve_sets for a ragged batch record (from corridor_batch): candidates of up to 64 segments."""
-        d = self.device
-        B, st = rec["B"], rec["seg_stride"]
-        o = dict(ctrl=torch.zeros((B, 12 * st), dtype=torch.float64, device=d),
-                 cost=torch.empty(B, dtype=torch.float64, device=d),
-                 status=torch.empty(B, dtype=torch.int32, device=d), iters=torch.empty(B, dtype=torch.int32, device=d))
-        return self._sets_call(B, st, sets, set_index, rec, rec["seg_count"], o, warm, keep_multipliers, options)
+    # ---- derivatives of a solve ---------------------------------------------------------------
+    def _derivative_args(self, what, r, shared_or_sets, out, set_index):
+        """What solve_vjp and solve_jvp check alike; returns the list of parameter sets."""
+        if set_index is not None:
+            _check_index(set_index, r.B)
+        if out.get("lam") is None:
+            raise ValueError("%s needs the solve's multipliers: solve with keep_multipliers=True" % what)
+        return _sets_of(shared_or_sets)
 
     def solve_vjp(self, dbatch_or_rec, shared_or_sets, out, ctrl_bar, cost_bar, set_index=None):
         """Gradients of a solve (btrapz_solve_vjp_device).  dbatch_or_rec: the DeviceBatch or ragged record that was solved;
@@ -285,31 +311,19 @@ class BatchSolver:
         [B, 12 S] / cost_bar [B]: cotangents (either may be None).  Returns a dict of device tensors: "seg"
         [NUM_SEG_FIELDS, B, S] (field 0 is 0), "init" [B, 6], "ref_end" [B, 2], "dl_bounds" [B, 10], "shared" [B, 20] per
         candidate (layout.Shared.as_array order, without delta)."""
-        if isinstance(dbatch_or_rec, dict):
-            B, S, seg_count = dbatch_or_rec["B"], dbatch_or_rec["seg_stride"], dbatch_or_rec["seg_count"]
-            seg, init, ref_end, dl = (dbatch_or_rec[k] for k in ("seg", "init", "ref_end", "dl_bounds"))
-        else:
-            B, S, seg_count = dbatch_or_rec.B, dbatch_or_rec.S, None
-            seg, init, ref_end, dl = dbatch_or_rec.seg, dbatch_or_rec.init, dbatch_or_rec.ref_end, dbatch_or_rec.dl_bounds
-        sets = list(shared_or_sets) if isinstance(shared_or_sets, (list, tuple)) else [shared_or_sets]
-        if set_index is not None:
-            assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
-        if out.get("lam") is None:
-            raise ValueError("solve_vjp needs the solve's multipliers: solve with keep_multipliers=True")
+        r = self._record(dbatch_or_rec)
+        B, S = r.B, r.S
+        sets = self._derivative_args("solve_vjp", r, shared_or_sets, out, set_index)
         chk = lambda t, shape: None if t is None else (t if (t.dtype == torch.float64 and t.is_contiguous() and
                                                             tuple(t.shape) == shape) else
                                                        t.to(self.device, dtype=torch.float64).reshape(shape).contiguous())
         ctrl_bar = chk(ctrl_bar, (B, 12 * S)); cost_bar = chk(cost_bar, (B,))
-        d = self.device
-        g = dict(seg=torch.empty((L.NUM_SEG_FIELDS, B, S), dtype=torch.float64, device=d),
-                 init=torch.empty((B, 6), dtype=torch.float64, device=d),
-                 ref_end=torch.empty((B, 2), dtype=torch.float64, device=d),
-                 dl_bounds=torch.empty((B, 10), dtype=torch.float64, device=d),
-                 shared=torch.empty((B, 20), dtype=torch.float64, device=d))
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.solve_vjp_device(B, S, sets, set_index, seg, seg_count, init, ref_end, dl, out["ctrl"], out["lam"],
-                                  out["status"], ctrl_bar, cost_bar, g_seg=g["seg"], g_init=g["init"],
-                                  g_ref_end=g["ref_end"], g_dl_bounds=g["dl_bounds"], g_shared=g["shared"], stream=stream)
+        g = dict(seg=self._empty(L.NUM_SEG_FIELDS, B, S), init=self._empty(B, 6), ref_end=self._empty(B, 2),
+                 dl_bounds=self._empty(B, 10), shared=self._empty(B, 20))
+        self.ctx.solve_vjp_device(B, S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, out["ctrl"],
+                                  out["lam"], out["status"], ctrl_bar, cost_bar, g_seg=g["seg"], g_init=g["init"],
+                                  g_ref_end=g["ref_end"], g_dl_bounds=g["dl_bounds"], g_shared=g["shared"],
+                                  stream=self._stream())
         return g
 
     def solve_jvp(self, dbatch_or_rec, shared_or_sets, out, tangents, set_index=None):
@@ -318,59 +332,45 @@ class BatchSolver:
         with any of "seg" [T, NUM_SEG_FIELDS, B, S] (field 0 is ignored), "init" [T, B, 6], "ref_end" [T, B, 2],
         "dl_bounds" [T, B, 10], "shared" [T, B, 20] (per candidate, layout.Shared.as_array order without delta); a missing
         one is zero.  Returns {"ctrl": [T, B, 12 S], "cost": [T, B]}, device tensors."""
-        if isinstance(dbatch_or_rec, dict):
-            B, S, seg_count = dbatch_or_rec["B"], dbatch_or_rec["seg_stride"], dbatch_or_rec["seg_count"]
-            seg, init, ref_end, dl = (dbatch_or_rec[k] for k in ("seg", "init", "ref_end", "dl_bounds"))
-        else:
-            B, S, seg_count = dbatch_or_rec.B, dbatch_or_rec.S, None
-            seg, init, ref_end, dl = dbatch_or_rec.seg, dbatch_or_rec.init, dbatch_or_rec.ref_end, dbatch_or_rec.dl_bounds
-        sets = list(shared_or_sets) if isinstance(shared_or_sets, (list, tuple)) else [shared_or_sets]
-        if set_index is not None:
-            assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
-        if out.get("lam") is None:
-            raise ValueError("solve_jvp needs the solve's multipliers: solve with keep_multipliers=True")
+        r = self._record(dbatch_or_rec)
+        B, S = r.B, r.S
+        sets = self._derivative_args("solve_jvp", r, shared_or_sets, out, set_index)
         unknown = set(tangents) - {"seg", "init", "ref_end", "dl_bounds", "shared"}
         if unknown:
             raise ValueError("unknown tangents: %s" % sorted(unknown))
         given = {k: v for k, v in tangents.items() if v is not None}
         T = next(iter(given.values())).shape[0] if given else 0
-        d = self.device
         shapes = dict(seg=(T, L.NUM_SEG_FIELDS, B, S), init=(T, B, 6), ref_end=(T, B, 2), dl_bounds=(T, B, 10), shared=(T, B, 20))
         tan = {}
         for k, v in given.items():
             if tuple(v.shape) != shapes[k]:
                 raise ValueError("tangent %r: shape %s, expected %s" % (k, tuple(v.shape), shapes[k]))
-            tan[k] = v.to(d, dtype=torch.float64).contiguous()
-        o = dict(ctrl=torch.empty((max(T, 0), B, 12 * S), dtype=torch.float64, device=d),
-                 cost=torch.empty((max(T, 0), B), dtype=torch.float64, device=d))
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.solve_jvp_device(B, S, sets, set_index, seg, seg_count, init, ref_end, dl, out["ctrl"], out["lam"],
-                                  out["status"], T, seg_dot=tan.get("seg"), init_dot=tan.get("init"),
+            tan[k] = self._f64(v)
+        o = dict(ctrl=self._empty(max(T, 0), B, 12 * S), cost=self._empty(max(T, 0), B))
+        self.ctx.solve_jvp_device(B, S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, out["ctrl"],
+                                  out["lam"], out["status"], T, seg_dot=tan.get("seg"), init_dot=tan.get("init"),
                                   ref_end_dot=tan.get("ref_end"), dl_bounds_dot=tan.get("dl_bounds"),
-                                  shared_dot=tan.get("shared"), ctrl_dot=o["ctrl"], cost_dot=o["cost"], stream=stream)
+                                  shared_dot=tan.get("shared"), ctrl_dot=o["ctrl"], cost_dot=o["cost"], stream=self._stream())
         return o
 
+    # ---- scores, samples, states and their derivatives ----------------------------------------
     def _cost_args(self, rec, shared_or_sets, ctrl, s_ref, l_ref, status, set_index):
-        if isinstance(rec, dict):
-            B, S, seg_count, seg, init = rec["B"], rec["seg_stride"], rec["seg_count"], rec["seg"], rec["init"]
-        else:
-            B, S, seg_count, seg, init = rec.B, rec.S, None, rec.seg, rec.init
-        sets = list(shared_or_sets) if isinstance(shared_or_sets, (list, tuple)) else [shared_or_sets]
-        d = self.device
-        f = lambda t: t.to(d, dtype=torch.float64).contiguous()
+        r = self._record(rec)
+        B, S = r.B, r.S
         t = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
-        s_ref, l_ref = f(t(s_ref)), f(t(l_ref))
+        s_ref, l_ref = self._f64(t(s_ref)), self._f64(t(l_ref))
         if s_ref.shape != l_ref.shape or s_ref.dim() not in (1, 2) or (s_ref.dim() == 2 and s_ref.shape[0] != B):
             raise ValueError("s_ref / l_ref: [N] (one line for every candidate) or [B, N]")
         N = s_ref.shape[-1]
         if set_index is not None:
-            assert set_index.dtype == torch.int32 and set_index.is_contiguous() and set_index.numel() == B
+            _check_index(set_index, B)
         if status is not None:
-            assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B
-        ctrl = f(ctrl)
+            _check_index(status, B)
+        ctrl = self._f64(ctrl)
         assert tuple(ctrl.shape) == (B, 12 * S), ctrl.shape
-        return dict(B=B, seg_stride=S, sets=sets, set_index=set_index, seg=seg, seg_count=seg_count, init=init, ctrl=ctrl,
-                    status=status, N=N, s_ref=s_ref, l_ref=l_ref, ref_stride=N if s_ref.dim() == 2 else 0)
+        return dict(B=B, seg_stride=S, sets=_sets_of(shared_or_sets), set_index=set_index, seg=r.seg, seg_count=r.seg_count,
+                    init=r.init, ctrl=ctrl, status=status, N=N, s_ref=s_ref, l_ref=l_ref,
+                    ref_stride=N if s_ref.dim() == 2 else 0)
 
     def traj_cost(self, rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, status=None, set_index=None):
         """a_cost -- the score find_traj returns -- of every candidate's sampled trajectory (btrapz_traj_cost_device).
@@ -379,10 +379,8 @@ class BatchSolver:
         (int32 [B], e.g. the solve's): candidates outside {1, 2} are not scored.  Returns (a_cost [B], n_points [B]) device
         tensors; a candidate that is not scored has +inf and 0."""
         a = self._cost_args(rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, status, set_index)
-        cost = torch.empty(a["B"], dtype=torch.float64, device=self.device)
-        npts = torch.empty(a["B"], dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx.traj_cost_device(**a, a_cost=cost, n_points=npts, stream=stream)
+        cost, npts = self._empty(a["B"]), self._empty(a["B"], dtype=torch.int32)
+        self.ctx.traj_cost_device(**a, a_cost=cost, n_points=npts, stream=self._stream())
         return cost, npts
 
     def traj_cost_vjp(self, rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, a_cost_bar, status=None, set_index=None):
@@ -390,62 +388,53 @@ class BatchSolver:
         tensors: "ctrl" [B, 12 S], "init" [B, 6], "params" [B, 20] per candidate (layout.Shared.as_array order, without
         delta), "s_ref" / "l_ref" [B, N] per candidate (also for a shared line: sum the rows)."""
         a = self._cost_args(rec_or_dbatch, shared_or_sets, ctrl, s_ref, l_ref, status, set_index)
-        B, S, N, d = a["B"], a["seg_stride"], a["N"], self.device
-        abar = torch.as_tensor(a_cost_bar).to(d, dtype=torch.float64).reshape(B).contiguous()
-        g = dict(ctrl=torch.empty((B, 12 * S), dtype=torch.float64, device=d),
-                 init=torch.empty((B, 6), dtype=torch.float64, device=d),
-                 params=torch.empty((B, 20), dtype=torch.float64, device=d),
-                 s_ref=torch.empty((B, N), dtype=torch.float64, device=d),
-                 l_ref=torch.empty((B, N), dtype=torch.float64, device=d))
-        stream = torch.cuda.current_stream(d).cuda_stream
+        B, S, N = a["B"], a["seg_stride"], a["N"]
+        abar = torch.as_tensor(a_cost_bar).to(self.device, dtype=torch.float64).reshape(B).contiguous()
+        g = dict(ctrl=self._empty(B, 12 * S), init=self._empty(B, 6), params=self._empty(B, 20), s_ref=self._empty(B, N),
+                 l_ref=self._empty(B, N))
         self.ctx.traj_cost_vjp_device(**a, a_cost_bar=abar, ctrl_bar=g["ctrl"], init_bar=g["init"], params_bar=g["params"],
-                                      s_ref_bar=g["s_ref"], l_ref_bar=g["l_ref"], stream=stream)
+                                      s_ref_bar=g["s_ref"], l_ref_bar=g["l_ref"], stream=self._stream())
         return g
 
     def argmin(self, cost, group=None, index_base=0):
         """Arg-min of cost over contiguous groups (default: the whole batch). Device tensors."""
         B = cost.numel()
         group = B if group is None else group
-        best_idx = torch.empty(B // group, dtype=torch.int64, device=self.device)
-        best_cost = torch.empty(B // group, dtype=torch.float64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx.argmin_device(B, group, index_base, cost, best_idx, best_cost, stream=stream)
+        best_idx, best_cost = self._empty(B // group, dtype=torch.int64), self._empty(B // group)
+        self.ctx.argmin_device(B, group, index_base, cost, best_idx, best_cost, stream=self._stream())
         return best_idx, best_cost
 
     def sample(self, dbatch, ctrl, sel, delta):
-        """Bernstein sampling (solve_3d.cc:1279-1392) of the selected candidates."""
+        """Bernstein sampling (solve_3d.cc:1279-1392) of the selected candidates of a DeviceBatch or a ragged record
+        (btrapz_sample_device / btrapz_sample_ragged_device) -> (out [nsel, 6, max_points], npoints [nsel])."""
+        r = self._record(dbatch)
         sel = sel.to(self.device, dtype=torch.int64).contiguous()
-        t = dbatch.seg[L.F_T]
+        t = r.seg[L.F_T]
+        if r.seg_count is not None:
+            t = t * (torch.arange(r.S, device=self.device)[None, :] < r.seg_count[:, None])
         max_points = int(torch.floor(t / delta + 1e-9).sum(1).max().item()) + 2
-        out = torch.zeros((sel.numel(), 6, max_points), dtype=torch.float64, device=self.device)
-        npts = torch.zeros(sel.numel(), dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx.sample_device(dbatch.B, dbatch.S, delta, dbatch.seg, dbatch.init, ctrl, sel, max_points, out, npts,
-                               stream=stream)
+        out, npts = self._zeros(sel.numel(), 6, max_points), self._zeros(sel.numel(), dtype=torch.int32)
+        if r.seg_count is None:
+            self.ctx.sample_device(r.B, r.S, delta, r.seg, r.init, ctrl, sel, max_points, out, npts, stream=self._stream())
+        else:
+            self.ctx.sample_ragged_device(r.B, r.S, r.seg_count, delta, r.seg, r.init, ctrl, sel, max_points, out, npts,
+                                          stream=self._stream())
         return out, npts
-
-    def _layout_of(self, rec_or_dbatch):
-        if isinstance(rec_or_dbatch, dict):
-            return rec_or_dbatch["B"], rec_or_dbatch["seg_stride"], rec_or_dbatch.get("seg_count"), rec_or_dbatch["seg"]
-        return rec_or_dbatch.B, rec_or_dbatch.S, None, rec_or_dbatch.seg
 
     def sample_vjp(self, rec_or_dbatch, sel, delta, out_bar, want_ctrl=True, want_init=True):
         """Vector-Jacobian product of sample (btrapz_sample_vjp_device).  rec_or_dbatch: the DeviceBatch or ragged record
         that was sampled; sel: the selection of the forward; out_bar [nsel, 6, max_points]: the cotangent of the samples
         (max_points is read off its shape).  Returns a dict of device tensors with ONE ROW PER SELECTION -- "ctrl"
         [nsel, 12 S] and "init" [nsel, 6]; a candidate that sel names twice has two rows, which the caller sums."""
-        B, S, seg_count, seg = self._layout_of(rec_or_dbatch)
-        d = self.device
-        sel = sel.to(d, dtype=torch.int64).contiguous()
-        out_bar = out_bar.to(d, dtype=torch.float64).contiguous()
+        r = self._record(rec_or_dbatch)
+        sel = sel.to(self.device, dtype=torch.int64).contiguous()
+        out_bar = self._f64(out_bar)
         n = sel.numel()
         if out_bar.dim() != 3 or out_bar.shape[0] != n or out_bar.shape[1] != 6:
             raise ValueError("out_bar: [nsel, 6, max_points]")
-        g = dict(ctrl=torch.empty((n, 12 * S), dtype=torch.float64, device=d) if want_ctrl else None,
-                 init=torch.empty((n, 6), dtype=torch.float64, device=d) if want_init else None)
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.sample_vjp_device(B, S, seg_count, delta, seg, sel, out_bar.shape[2], out_bar, ctrl_bar=g["ctrl"],
-                                   init_bar=g["init"], stream=stream)
+        g = dict(ctrl=self._empty(n, 12 * r.S) if want_ctrl else None, init=self._empty(n, 6) if want_init else None)
+        self.ctx.sample_vjp_device(r.B, r.S, r.seg_count, delta, r.seg, sel, out_bar.shape[2], out_bar, ctrl_bar=g["ctrl"],
+                                   init_bar=g["init"], stream=self._stream())
         return g
 
     def eval_states_vjp(self, rec_or_dbatch, ctrl, times, x_bar, want_ctrl=True, want_times=True):
@@ -453,16 +442,13 @@ class BatchSolver:
         record; ctrl [B, 12 S]; times [B, n_times]; x_bar [B, 2, n_times, 3]: the cotangent of the states.  Returns a dict
         of device tensors: "ctrl" [B, 12 S] and "times" [B, n_times], the derivative along the trajectory (0 for a time
         that is not > 0)."""
-        B, S, seg_count, seg = self._layout_of(rec_or_dbatch)
-        d = self.device
-        f = lambda t: t.to(d, dtype=torch.float64).contiguous()
-        times, x_bar, ctrl = f(times), f(x_bar), f(ctrl)
+        r = self._record(rec_or_dbatch)
+        B, S = r.B, r.S
+        times, x_bar, ctrl = self._f64(times), self._f64(x_bar), self._f64(ctrl)
         n = times.shape[1]
         if tuple(times.shape) != (B, n) or tuple(x_bar.shape) != (B, 2, n, 3) or tuple(ctrl.shape) != (B, 12 * S):
             raise ValueError("times [B, n_times], x_bar [B, 2, n_times, 3], ctrl [B, 12 S]")
-        g = dict(ctrl=torch.empty((B, 12 * S), dtype=torch.float64, device=d) if want_ctrl else None,
-                 times=torch.empty((B, n), dtype=torch.float64, device=d) if want_times else None)
-        stream = torch.cuda.current_stream(d).cuda_stream
-        self.ctx.eval_states_vjp_device(B, S, seg_count, seg, ctrl, n, times, x_bar, ctrl_bar=g["ctrl"],
-                                        times_bar=g["times"], stream=stream)
+        g = dict(ctrl=self._empty(B, 12 * S) if want_ctrl else None, times=self._empty(B, n) if want_times else None)
+        self.ctx.eval_states_vjp_device(B, S, r.seg_count, r.seg, ctrl, n, times, x_bar, ctrl_bar=g["ctrl"],
+                                        times_bar=g["times"], stream=self._stream())
         return g

@@ -22,10 +22,21 @@ def built():
     return native.lib()
 
 
+def header_without_comments():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
 def declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(btrapz_[a-z_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(btrapz_[a-z_]+)\s*\(", header_without_comments())))
+
+
+def declared_prototypes():
+    """name -> (return type as written, number of parameters) of every prototype of the header."""
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][A-Za-z_ ]*?[\s*]+)\b(btrapz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", header_without_comments()):
+        ret, name, params = " ".join(m.group(1).replace("*", " * ").split()), m.group(2), m.group(3).strip()
+        out[name] = (ret, 0 if params == "void" else len(params.split(",")))
+    return out
 
 
 def test_every_declared_symbol_is_exported(built):
@@ -34,6 +45,36 @@ def test_every_declared_symbol_is_exported(built):
     for n in names:
         assert hasattr(built, n), n
     assert set(names) == set(native.EXPORTS)
+
+
+def test_every_declared_function_has_a_prototype_entry():
+    protos = declared_prototypes()
+    assert len(protos) == 57 and set(protos) == set(declared_functions())
+    assert set(protos) == set(native.PROTOTYPES) == set(native.EXPORTS)
+
+
+def test_prototype_argument_counts_follow_the_header(built):
+    """A wrong count in ctypes is silent garbage, not an error: hold every entry to the header."""
+    for name, (_, n_params) in declared_prototypes().items():
+        assert len(getattr(built, name).argtypes) == n_params, name
+
+
+def test_prototype_return_types_follow_the_header(built):
+    ctype = {"int": C.c_int, "double": C.c_double, "const char *": C.c_char_p, "long long": C.c_longlong, "void": None}
+    for name, (ret, _) in declared_prototypes().items():
+        assert ret in ctype, (name, ret)
+        assert getattr(built, name).restype is ctype[ret], (name, ret)
+
+
+def test_python_layer_has_one_marshalling_path():
+    """diff.py goes through BatchSolver's public methods on one batch record; native.py and solver.py convert tensors to
+    pointers with the module's helpers, not with a lambda per method."""
+    pkg = os.path.join(ROOT, "spectral_amd")
+    diff = open(os.path.join(pkg, "diff.py")).read()
+    assert "SimpleNamespace" not in diff and "solver._" not in diff
+    for f in ("native.py", "solver.py"):
+        for line in open(os.path.join(pkg, f)):
+            assert not ("lambda" in line and "data_ptr" in line), (f, line)
 
 
 @pytest.mark.parametrize("lib", ["libtrp.so", "libcub.so", "libbtrapz.so"])

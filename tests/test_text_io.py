@@ -9,14 +9,6 @@ import numpy as np
 from spectral_amd import native
 
 
-def _lib():
-    l = native.lib()
-    l.btrapz_debug_parse_double.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
-    l.btrapz_debug_parse_double.restype = C.c_double
-    l.btrapz_debug_format_fixed.argtypes = [C.c_double, C.c_char_p]
-    return l
-
-
 def parse(l, text):
     n = C.c_int(-1)
     v = l.btrapz_debug_parse_double(text.encode(), C.byref(n))
@@ -24,7 +16,7 @@ def parse(l, text):
 
 
 def test_scanner_equals_strtod():
-    l = _lib()
+    l = native.lib()
     libc = C.CDLL(None)
     libc.strtod.restype = C.c_double
     libc.strtod.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -57,7 +49,7 @@ def test_scanner_equals_strtod():
 
 
 def test_writer_equals_printf():
-    l = _lib()
+    l = native.lib()
     buf = C.create_string_buffer(336)
     rng = np.random.default_rng(1)
     vals = [0.0, -0.0, 0.0005, -0.0005, 0.0015, 0.0025, 0.0625, -0.0625, 0.1235, 1.0005, 2.5, 1e-9, -1e-9, -0.0004, 0.9995, 0.99949999999, 999.9995,
