@@ -532,7 +532,9 @@ int btrapz_prism_bounds_device(btrapz_ctx *ctx, int B, int P, int N, const btrap
 int btrapz_prism_bounds_vjp_device(btrapz_ctx *ctx, int B, int P, int N, const btrapz_road *road, const double *prisms,
                                    int O, const double *s_bounds_bar, const double *l_bounds_bar, double *prisms_bar,
                                    void *stream);
-/* The same on the host (no GPU, no context): every pointer a host pointer. */
+/* The same on the host (no GPU, no context): every pointer a host pointer.
+ * (Forward mode -- Jacobian-vector products of this stage and of the corridor stage -- is declared in a header of its own,
+ * next to this one.) */
 int btrapz_prism_bounds_vjp_host(int B, int P, int N, const btrapz_road *road, const double *prisms, int O,
                                  const double *s_bounds_bar, const double *l_bounds_bar, double *prisms_bar);
 

@@ -13,6 +13,8 @@
 #include <cstddef>
 #include <type_traits>
 #include "btrapz_device.h"
+#include "corridor_jvp.h"
+#include "../../include/btrapz_hip_stage_jvp.h"
 #include "prism_core.h"
 
 using namespace btrapz;
@@ -1488,6 +1490,68 @@ BTRAPZ_EXPORT int btrapz_corridor_batch_vjp_device(btrapz_ctx *c, int variant, i
     a.pass = 1; a.cap_o = cap_o_big; a.cap_sel = cap_sel_big;
     const unsigned blocks = B < 1024 ? (unsigned)B : 1024u;
     hipLaunchKernelGGL(corridor_vjp_kernel, dim3(blocks), dim3(64), corridor_vjp_lds(N, num_obs, a.cap_o, a.cap_sel, seg_stride, a.staged).bytes, stream, a);
+    HIPCHK(c, hipGetLastError());
+  }
+  return BTRAPZ_OK;
+}
+
+// The forward-mode derivative of the stage (corridor_jvp.hip, include/btrapz_hip_stage_jvp.h): the backward pass's two
+// passes with the same capacities; every output entry is written by the pass that settles its candidate, nothing is zeroed.
+BTRAPZ_EXPORT int btrapz_corridor_batch_jvp_device(btrapz_ctx *c, int variant, int B, int N, int num_obs, double delta,
+                                                const double *s_bounds, const double *l_bounds, const double *ds_bounds,
+                                                const double *dl_bounds_knots, const double *s_ref, const double *l_ref,
+                                                int seg_stride, int T, const btrapz_knot_tangents *tan, double *seg_dot,
+                                                double *ref_end_dot, double *dl_bounds_dot, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (variant < 0 || variant > 1 || B < 1 || N < 3 || num_obs < 1 || !(delta > 0) || seg_stride < 1) {
+    c->err = "invalid argument: variant 0 or 1, B >= 1, N >= 3, num_obs >= 1, delta > 0 and seg_stride >= 1";
+    return BTRAPZ_EINVAL;
+  }
+  if (N > 512 || num_obs > 64 || seg_stride > BTRAPZ_MAX_SEGMENTS) {
+    c->err = "invalid argument: N > 512, num_obs > 64 or seg_stride > BTRAPZ_MAX_SEGMENTS -- beyond the wave-wide corridor kernels; "
+             "the serial one-lane-per-candidate path of the stage is not differentiated";
+    return BTRAPZ_EINVAL;
+  }
+  if (T < 1 || T > BTRAPZ_MAX_TANGENTS) { c->err = "invalid argument: T must be in 1..BTRAPZ_MAX_TANGENTS"; return BTRAPZ_EINVAL; }
+  if (!s_bounds || !l_bounds || !ds_bounds || !dl_bounds_knots || !s_ref || !l_ref) {
+    c->err = "invalid argument: s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref and l_ref must be non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (!tan || (!tan->s_bounds && !tan->l_bounds && !tan->ds_bounds && !tan->dl_bounds_knots && !tan->s_ref && !tan->l_ref)) {
+    c->err = "invalid argument: no tangent given (tangents, or every pointer of it, is null)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!seg_dot && !ref_end_dot && !dl_bounds_dot) {
+    c->err = "invalid argument: seg_dot, ref_end_dot and dl_bounds_dot are all null";
+    return BTRAPZ_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  GROW(c, d_vjp_retry, sizeof(int) * ((size_t)B + 1));
+  HIPCHK(c, hipMemsetAsync(c->d_vjp_retry, 0, sizeof(int), stream));
+  CorridorJvpArgs a;
+  memset(&a, 0, sizeof a);
+  a.B = B; a.N = N; a.num_obs = num_obs; a.variant = variant; a.seg_stride = seg_stride; a.T = T; a.delta = delta;
+  a.s_bounds = s_bounds; a.l_bounds = l_bounds; a.ds_bounds = ds_bounds; a.s_ref = s_ref; a.l_ref = l_ref;
+  a.s_dot = tan->s_bounds; a.l_dot = tan->l_bounds; a.ds_dot = tan->ds_bounds; a.dl_knots_dot = tan->dl_bounds_knots;
+  a.sref_dot = tan->s_ref; a.lref_dot = tan->l_ref;
+  a.seg_dot = seg_dot; a.ref_end_dot = ref_end_dot; a.dl10_dot = dl_bounds_dot;
+  a.staged = sizeof(double) * 2 * (size_t)N * num_obs <= 24 * 1024 ? 1 : 0;
+  a.retry_count = c->d_vjp_retry; a.retry_list = c->d_vjp_retry + 1;
+  // (the forward's capacities: launch_corridor_stage)
+  const int cap_o_big = 160 / num_obs, cap_sel_big = 64;
+  int cap_o_small = (N - 1) / 10 + (N <= 128 ? 3 : 5), cap_sel_small = 2 * seg_stride < 16 ? 16 : 2 * seg_stride;
+  if (cap_o_small > cap_o_big) cap_o_small = cap_o_big;
+  if (cap_sel_small > cap_sel_big) cap_sel_small = cap_sel_big;
+  const bool two_pass = cap_o_small < cap_o_big || cap_sel_small < cap_sel_big;
+  a.pass = 0; a.cap_o = cap_o_small; a.cap_sel = cap_sel_small;
+  if (!two_pass) { a.retry_list = nullptr; a.retry_count = nullptr; }
+  hipLaunchKernelGGL(corridor_jvp_kernel, dim3(B), dim3(64), corridor_vjp_lds(N, num_obs, a.cap_o, a.cap_sel, seg_stride, a.staged).bytes, stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (two_pass) {
+    a.pass = 1; a.cap_o = cap_o_big; a.cap_sel = cap_sel_big;
+    const unsigned blocks = B < 1024 ? (unsigned)B : 1024u;
+    hipLaunchKernelGGL(corridor_jvp_kernel, dim3(blocks), dim3(64), corridor_vjp_lds(N, num_obs, a.cap_o, a.cap_sel, seg_stride, a.staged).bytes, stream, a);
     HIPCHK(c, hipGetLastError());
   }
   return BTRAPZ_OK;

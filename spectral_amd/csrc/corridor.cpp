@@ -3,6 +3,7 @@
 
 #include "corridor_core.h"
 #include "corridor_vjp_core.h"
+#include "../../include/btrapz_hip_stage_jvp.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -285,5 +286,51 @@ extern "C" __attribute__((visibility("default"))) int btrapz_corridor_vjp_host(
       const int i = j >> 1, ii = i > N - 1 ? N - 1 : i;
       out->dl_bounds_knots[2 * ii + (j & 1)] += dl_bounds_bar[j];
     }
+  return BTRAPZ_OK;
+}
+
+// ---- forward-mode derivative of the corridor stage, one candidate on the host (the twin of corridor_jvp_kernel) ----------
+// decide_with_provenance, then segment_tangent on every segment and direction: the kernel's statements, the kernel's bits.
+extern "C" __attribute__((visibility("default"))) int btrapz_corridor_jvp_host(
+    int variant, int N, int num_obs, double delta, const double *s_bounds, const double *l_bounds, const double *ds_bounds,
+    const double *dl_bounds_knots, const double *s_ref, const double *l_ref, int seg_stride, int T,
+    const btrapz_knot_tangents *tangents, double *seg_dot, double *ref_end_dot, double *dl_bounds_dot, int *seg_count) {
+  using namespace btrapz;
+  if (variant < 0 || variant > 1 || N < 3 || N > VJP_MAX_KNOTS || num_obs < 1 || num_obs > VJP_MAX_OBS || !(delta > 0) || seg_stride < 1 ||
+      seg_stride > BTRAPZ_MAX_SEGMENTS || T < 1 || T > BTRAPZ_MAX_TANGENTS || !s_bounds || !l_bounds || !ds_bounds || !dl_bounds_knots ||
+      !s_ref || !l_ref || !tangents ||
+      (!tangents->s_bounds && !tangents->l_bounds && !tangents->ds_bounds && !tangents->dl_bounds_knots && !tangents->s_ref && !tangents->l_ref) ||
+      (!seg_dot && !ref_end_dot && !dl_bounds_dot))
+    return BTRAPZ_EINVAL;
+  std::vector<Seg> sel;
+  const int S = decide_with_provenance(variant, N, num_obs, delta, s_bounds, l_bounds, s_ref, l_ref, seg_stride, sel);
+  if (seg_count) *seg_count = S;
+  const bool has = S > 0;
+  const size_t pairs = (size_t)num_obs * N * 2;
+  std::vector<SegmentReads> reads;
+  for (int k = 0; k < (has ? S : 0); k++) reads.push_back(segment_reads(N, k, sel[k], ds_bounds));
+  for (int t = 0; t < T; t++) {
+    const KnotTangentSource src{tangents->s_bounds ? tangents->s_bounds + t * pairs : nullptr,
+                                tangents->l_bounds ? tangents->l_bounds + t * pairs : nullptr,
+                                tangents->ds_bounds ? tangents->ds_bounds + (size_t)t * N * 2 : nullptr,
+                                tangents->s_ref ? tangents->s_ref + (size_t)t * N : nullptr,
+                                tangents->l_ref ? tangents->l_ref + (size_t)t * N : nullptr, N};
+    if (seg_dot)
+      for (int k = 0; k < seg_stride; k++) {
+        double out[BTRAPZ_NUM_SEG_FIELDS];
+        if (has && k < S) segment_tangent(variant, delta, reads[k], src, out);
+        else for (int f = 0; f < BTRAPZ_NUM_SEG_FIELDS; f++) out[f] = 0.0;
+        for (int f = 0; f < BTRAPZ_NUM_SEG_FIELDS; f++) seg_dot[((size_t)t * BTRAPZ_NUM_SEG_FIELDS + f) * seg_stride + k] = out[f];
+      }
+    if (ref_end_dot) {
+      ref_end_dot[2 * t] = has ? src.sr(N - 1) : 0.0;
+      ref_end_dot[2 * t + 1] = has ? src.lr(N - 1) : 0.0;
+    }
+    if (dl_bounds_dot)
+      for (int j = 0; j < 10; j++) {
+        const int i = j >> 1, ii = i > N - 1 ? N - 1 : i;
+        dl_bounds_dot[10 * t + j] = has && tangents->dl_bounds_knots ? tangents->dl_bounds_knots[((size_t)t * N + ii) * 2 + (j & 1)] : 0.0;
+      }
+  }
   return BTRAPZ_OK;
 }

@@ -10,6 +10,7 @@
 // kernels' limits (64 obstacles, 512 knots, hence at most 51 pieces).
 // segment_adjoint() below is the whole per-segment transpose; corridor.cpp (btrapz_corridor_vjp_host) and
 // corridor_vjp.hip (corridor_vjp_kernel) call it on the segments their -- identical -- decisions leave.
+// segment_tangent() is the same map read forwards, one direction at a time (btrapz_corridor_jvp_host, corridor_jvp.hip).
 #ifndef BTRAPZ_CORRIDOR_VJP_CORE_H
 #define BTRAPZ_CORRIDOR_VJP_CORE_H
 
@@ -104,6 +105,59 @@ BTRAPZ_HD void segment_adjoint(int variant, int N, double delta, int k, const Se
     sink.add(VJP_G_LREF, 1, r1, yk);
   }
 #undef BAR_
+}
+
+// ---- forward mode (corridor_jvp.hip, btrapz_corridor_jvp_host): the same rules read forwards ----
+// One direction's tangents of one candidate's six input arrays, laid out as the inputs; a null array is zero.
+struct KnotTangentSource {
+  const double *s, *l;        // [O][N][2]
+  const double *ds;           // [N][2]
+  const double *sref, *lref;  // [N]
+  int N;
+  BTRAPZ_HD double sb(int o, int i, int j) const { return s ? s[((size_t)o * N + i) * 2 + j] : 0.0; }
+  BTRAPZ_HD double lb(int o, int i, int j) const { return l ? l[((size_t)o * N + i) * 2 + j] : 0.0; }
+  BTRAPZ_HD double dsb(int i, int j) const { return ds ? ds[(size_t)i * 2 + j] : 0.0; }
+  BTRAPZ_HD double sr(int i) const { return sref ? sref[i] : 0.0; }
+  BTRAPZ_HD double lr(int i) const { return lref ? lref[i] : 0.0; }
+};
+// Where output segment k reads: the same for every direction, so found once per segment.
+struct SegmentReads { int o, i0, h, i1, at_lo, at_hi, r0, r1; };
+BTRAPZ_HD SegmentReads segment_reads(int N, int k, const Seg &c, const double *dsb) {
+  SegmentReads r;
+  r.o = provenance_obstacle(c.count); r.i0 = provenance_knot(c.count); r.h = provenance_pieces(c.count);
+  r.i1 = r.i0 == 0 ? 1 : r.i0;
+  ds_extreme_knots(N, c.beg_t, c.end_t, dsb, r.at_lo, r.at_hi);
+  r.r0 = 10 * k > N - 1 ? N - 1 : 10 * k; r.r1 = 10 * k + 1 > N - 1 ? N - 1 : 10 * k + 1;
+  return r;
+}
+// The tangents of the record of one output segment for one direction: out[f], f < BTRAPZ_NUM_SEG_FIELDS (field 0: 0).
+template <class Source>
+BTRAPZ_HD void segment_tangent(int variant, double delta, const SegmentReads &r, const Source &src, double *out) {
+  out[BTRAPZ_F_T] = 0.0;
+  {
+    const double lo0 = src.sb(r.o, r.i0, 0), hi0 = src.sb(r.o, r.i0, 1);
+    const double dk = (src.sb(r.o, r.i0 + 1, 0) - lo0) / delta, uk = (src.sb(r.o, r.i0 + 1, 1) - hi0) / delta;
+    out[BTRAPZ_F_DOWN_SKEW] = dk; out[BTRAPZ_F_DOWN_BIAS] = lo0 + (double)r.h * dk;
+    out[BTRAPZ_F_UPP_SKEW] = uk; out[BTRAPZ_F_UPP_BIAS] = hi0 + (double)r.h * uk;
+  }
+  {
+    const double llo = src.lb(r.o, r.i0, 0), lhi = src.lb(r.o, r.i0, 1);
+    out[BTRAPZ_F_BEG_L] = llo; out[BTRAPZ_F_END_L] = lhi;
+    if (variant == 0) {
+      out[BTRAPZ_F_L_DOWN_BIAS] = llo; out[BTRAPZ_F_L_UPP_BIAS] = lhi;
+      out[BTRAPZ_F_L_DOWN_SKEW] = (src.lb(r.o, r.i1, 0) - src.lb(r.o, r.i1 - 1, 0)) / delta;
+      out[BTRAPZ_F_L_UPP_SKEW] = (src.lb(r.o, r.i1, 1) - src.lb(r.o, r.i1 - 1, 1)) / delta;
+    } else {
+      out[BTRAPZ_F_L_DOWN_BIAS] = 0.0; out[BTRAPZ_F_L_UPP_BIAS] = 0.0; out[BTRAPZ_F_L_DOWN_SKEW] = 0.0; out[BTRAPZ_F_L_UPP_SKEW] = 0.0;
+    }
+  }
+  out[BTRAPZ_F_DS_LO] = r.at_lo < 0 ? 0.0 : src.dsb(r.at_lo, 0);
+  out[BTRAPZ_F_DS_HI] = r.at_hi < 0 ? 0.0 : src.dsb(r.at_hi, 1);
+  {
+    const double x0 = src.sr(r.r0), y0 = src.lr(r.r0);
+    out[BTRAPZ_F_X_BIAS] = x0; out[BTRAPZ_F_X_SKEW] = (src.sr(r.r1) - x0) / delta;
+    out[BTRAPZ_F_Y_BIAS] = y0; out[BTRAPZ_F_Y_SKEW] = (src.lr(r.r1) - y0) / delta;
+  }
 }
 
 }  // namespace btrapz

@@ -11,6 +11,8 @@
 //            when an earlier candidate has its value or it is off: the provenance of an edge;
 //   the winner of each max / min of a strip's s bounds at a knot (prism_vjp_winners);
 //   the raw parameters t0, vel_s, vel_l, T of a car for the chain rule (prism_vjp_car_out).
+// The forward-mode derivative (prism_jvp.hip, prism_jvp_host.cpp) makes the same decisions with the same statements and
+// reads the chain rule forwards: prism_jvp_edge_owner, prism_jvp_edge_dot, prism_jvp_face_dot at the end of this file.
 // THE TWO-DECIMAL ROUNDING OF A FACE IS DIFFERENTIATED AS THE IDENTITY (straight-through): a face value at knot i counts as
 // s0 -+ l_safe + vel_s (i / rate - t0).
 #ifndef BTRAPZ_PRISM_VJP_CORE_H
@@ -186,6 +188,29 @@ BTRAPZ_HD void prism_vjp_car_out(const PrismVjpTab &t, int P, int q, double face
     g[5] = t.vl[q] * moving;
   }
   for (int k = 0; k < 8; k++) out[k] = g[k];
+}
+
+// ---- forward mode (prism_jvp.hip, prism_jvp_host.cpp): the rules of prism_vjp_car_out read forwards, per element ----
+// d: the tangents of one scene's cars for one direction, [P][6] = s0, l0, t0, vel_s, vel_l, T.
+// after phase 4, c < 2P + 2: owner[j] = the candidate that supplied edge j (every edge 0..strips has exactly one)
+BTRAPZ_HD void prism_jvp_edge_owner(const PrismVjpTab &t, int *owner, int c) {
+  if (t.slot[c] >= 0) owner[t.slot[c]] = c;
+}
+// the tangent of the edge candidate c supplied: l0_dot for the stationary end, (l0_dot + T vel_l_dot) + vel_l T_dot for
+// the end that is l0 + vel_l T -+ w_safe, 0 for the road's edges
+BTRAPZ_HD double prism_jvp_edge_dot(const PrismVjpTab &t, int P, int c, const double *d) {
+  if (c < 0 || c >= 2 * P) return 0.0;
+  const int q = c < P ? c : c - P;
+  const double *dq = d + (size_t)q * 6;
+  const bool moving = (t.vl[q] >= 0) == (c >= P);
+  if (!moving) return dq[1];
+  return (dq[1] + t.T[q] * dq[4]) + t.vl[q] * dq[5];
+}
+// the tangent of car q's face at knot i (rounding straight-through)
+BTRAPZ_HD double prism_jvp_face_dot(const PrismVjpTab &t, const btrapz_road &r, int q, int i, const double *d) {
+  const double *dq = d + (size_t)q * 6;
+  const double at = (double)i / r.knots_per_second;
+  return (dq[0] + dq[3] * (at - t.t0[q])) - t.vs[q] * dq[2];
 }
 
 }  // namespace btrapz

@@ -357,3 +357,96 @@ def prism_bounds(solver, prisms, N, O, road=None):
     differentiated as the identity (include/btrapz_hip.h lists the rules); `active` and `reserved` get 0, and so does every
     entry of a scene with more than O strips."""
     return _PrismBounds.apply(prisms, solver, int(N), int(O), road)
+
+
+# ---- forward mode from the scene: prisms -> bounds -> record -> control points (include/btrapz_hip_stage_jvp.h) -----------
+
+_KNOT_TANGENTS = ("ds_bounds", "dl_bounds_knots", "s_ref", "l_ref")
+_RECORD_TANGENTS = ("init", "shared")
+JVP_CHUNK = 32   # BTRAPZ_MAX_TANGENTS
+
+
+def scene_jacobian(solver, prisms, prisms_dot, ds_bounds, dl_bounds_knots, s_ref, l_ref, init, params, *, O, variant=0,
+                   delta=0.1, seg_stride=16, road=None, more=None):
+    """Directional derivatives of the planned trajectories with respect to the scene.  One forward pipeline --
+    prism_bounds -> corridor stage -> solve with its multipliers kept -- then, per chunk of at most 32 directions, one launch
+    per stage on that one solve: prism_bounds_jvp -> corridor_batch_jvp -> solve_jvp.
+
+    prisms [B, P, 8]; prisms_dot [T, B, P, 8]: T directions of the obstacle prisms (entries 6, 7 and inactive slots are not
+    read; None: zero, with `more`); ds_bounds, dl_bounds_knots [B, N, 2]; s_ref, l_ref [B, N]; init [B, 6]; params [20].
+    more: a dict of further tangents with the same leading axis T -- knot level "ds_bounds", "dl_bounds_knots" [T, B, N, 2],
+    "s_ref", "l_ref" [T, B, N]; record level "init" [T, B, 6], "shared" [T, B, 20].
+    Returns a dict: "ctrl" [B, 12 S], "cost", "status", "seg_count", "n_strips" [B], "dctrl" [T, B, 12 S], "dcost" [T, B], "rec"
+    (the batch record that was solved) and "out" (the solve's result dict).  The decisions of both stages are frozen and the
+    faces' rounding is straight-through; scenes without a corridor or a solution get zero tangents.
+    MEMORY: a chunk holds the dense bounds tangents, 2 x 16 min(T, 32) B O N bytes, until its solve_jvp has been issued; a
+    fused prisms -> record derivative would not need them."""
+    _check_params(params, None)
+    more = dict(more or {})
+    unknown = set(more) - set(_KNOT_TANGENTS) - set(_RECORD_TANGENTS)
+    if unknown:
+        raise ValueError("unknown tangents: %s" % sorted(unknown))
+    more = {k: v for k, v in more.items() if v is not None}
+    if prisms_dot is None and not more:
+        raise ValueError("no tangent given")
+    p, ds, dl, sr, lr, ini = _on(solver, prisms, ds_bounds, dl_bounds_knots, s_ref, l_ref, init)
+    B, N = p.shape[0], sr.shape[1]
+    T = prisms_dot.shape[0] if prisms_dot is not None else next(iter(more.values())).shape[0]
+    for k, v in more.items():
+        if v.shape[0] != T:
+            raise ValueError("tangent %r: %d directions, expected %d" % (k, v.shape[0], T))
+    sb, lb, n_strips = solver.prism_bounds(p, N, O, road=road)
+    staged = solver.corridor_batch_tensors(variant, N, delta, sb, lb, ds, dl, sr, lr, ini, seg_stride=seg_stride)
+    rec, sets, out = _solve_kept(solver, staged["seg"], staged["init"], staged["ref_end"], staged["dl_bounds"], params,
+                                 staged["seg_count"], None, variant, delta)
+    knots = (sb, lb, ds, dl, sr, lr)
+    dctrl, dcost = [], []
+    for t0 in range(0, T, JVP_CHUNK):
+        part = slice(t0, min(t0 + JVP_CHUNK, T))
+        tan = {k: _on(solver, more[k][part])[0] for k in _KNOT_TANGENTS if k in more}
+        if prisms_dot is not None:
+            tan["s_bounds"], tan["l_bounds"] = solver.prism_bounds_jvp(p, N, O, _on(solver, prisms_dot[part])[0], road=road)
+        rt = solver.corridor_batch_jvp(knots, variant, tan, delta=delta, seg_stride=seg_stride) if tan else {}
+        for k in _RECORD_TANGENTS:
+            if k in more:
+                rt[k] = _on(solver, more[k][part])[0]
+        j = solver.solve_jvp(rec, sets, out, rt)
+        dctrl.append(j["ctrl"]); dcost.append(j["cost"])
+    cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+    return dict(ctrl=out["ctrl"], cost=out["cost"], status=out["status"], seg_count=rec.seg_count, n_strips=n_strips,
+                dctrl=cat(dctrl), dcost=cat(dcost), rec=rec, out=out)
+
+
+def trajectory_spread(solver, prisms, sigma, ds_bounds, dl_bounds_knots, s_ref, l_ref, init, params, *, O, variant=0,
+                      delta=0.1, seg_stride=16, road=None, sel=None):
+    """First-order spread of the sampled trajectories under independent uncertainties of the obstacle prisms.  sigma
+    [B, P, 6]: standard deviations of s0, l0, t0, vel_s, vel_l, T of every car.  One unit direction per (car, parameter)
+    column that has a non-zero sigma in any scene -> scene_jacobian -> sample_jvp; the spread of sample y is
+    sqrt(sum_c (dy / dtheta_c sigma_c)^2), the columns added in ascending (car, parameter) order.  Other arguments as
+    scene_jacobian; sel: the scenes to sample (int64, default every scene in order).
+    Returns a dict: "traj" [nsel, 6, max_points] and "npoints" [nsel] (diff.sample's), "spread" [nsel, 6, max_points] (NaN
+    for a scene that is not solved), "columns" (the list of (car, parameter) pairs) and "jac" (scene_jacobian's dict)."""
+    d = solver.device
+    p, sg = _on(solver, prisms, sigma)
+    B, P = p.shape[0], p.shape[1]
+    if tuple(sg.shape) != (B, P, 6):
+        raise ValueError("sigma must be [B, P, 6] = %s, not %s" % ((B, P, 6), tuple(sg.shape)))
+    columns = [(q, k) for q in range(P) for k in range(6) if bool((sg[:, q, k] != 0).any())]
+    if not columns:
+        raise ValueError("sigma is zero everywhere")
+    pd = torch.zeros((len(columns), B, P, 8), dtype=torch.float64, device=d)
+    for c, (q, k) in enumerate(columns):
+        pd[c, :, q, k] = 1.0
+    jac = scene_jacobian(solver, p, pd, ds_bounds, dl_bounds_knots, s_ref, l_ref, init, params, O=O, variant=variant, delta=delta,
+                         seg_stride=seg_stride, road=road)
+    rec = jac["rec"]
+    sel = (torch.arange(B, device=d) if sel is None else sel.to(d)).to(torch.int64).contiguous()
+    traj, npts = solver.sample(rec, jac["ctrl"], sel, delta)
+    dy = sample_jvp(solver, jac["dctrl"], rec.seg, seg_count=rec.seg_count, sel=sel, delta=delta)
+    var = torch.zeros_like(traj)
+    for c, (q, k) in enumerate(columns):
+        var += (dy[c, :, :, :traj.shape[2]] * sg[sel, q, k][:, None, None]) ** 2
+    spread = torch.sqrt(var)
+    status = jac["status"][sel]
+    spread[(status != 1) & (status != 2)] = float("nan")
+    return dict(traj=traj, npoints=npts, spread=spread, columns=columns, jac=jac)

@@ -79,6 +79,12 @@ class CKnotGrads(C.Structure):
 KNOT_GRADS = ("s_bounds", "l_bounds", "ds_bounds", "dl_bounds_knots", "s_ref", "l_ref")
 
 
+class CKnotTangents(C.Structure):
+    """btrapz_knot_tangents (include/btrapz_hip_stage_jvp.h): pointers of the input tangents of
+    btrapz_corridor_batch_jvp_device (device) / btrapz_corridor_jvp_host (host), in KNOT_GRADS' order."""
+    _fields_ = CKnotGrads._fields_
+
+
 class CWarm(C.Structure):
     """btrapz_warm (include/btrapz_hip.h): optional warm start of a solve."""
     _fields_ = [("x0", C.c_void_p), ("lam0", C.c_void_p), ("lam_out", C.c_void_p),
@@ -214,6 +220,15 @@ PROTOTYPES = {
 }
 EXPORTS = tuple(PROTOTYPES)
 
+# Every function of include/btrapz_hip_stage_jvp.h, the same way (tests/test_abi_stage_jvp.py holds it to that header).
+PROTOTYPES_STAGE_JVP = {
+    "btrapz_prism_bounds_jvp_device": (_i, [_vp, _i, _i, _i, _road, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_prism_bounds_jvp_host": (_i, [_i, _i, _i, _road, _vp, _i, _i, _vp, _vp, _vp]),
+    "btrapz_corridor_batch_jvp_device": (_i, [_vp, _i, _i, _i, _i, _d] + _knots + [_i, _i, C.POINTER(CKnotTangents), _vp, _vp, _vp, _vp]),
+    "btrapz_corridor_jvp_host": (_i, [_i, _i, _i, _d] + _knots + [_i, _i, C.POINTER(CKnotTangents), _vp, _vp, _vp, _ip]),
+}
+EXPORTS_STAGE_JVP = tuple(PROTOTYPES_STAGE_JVP)
+
 
 def _ptr(t):
     """Device tensor -> its address as a c_void_p; None -> None (a NULL argument or struct field), always.  Keeps nothing
@@ -292,7 +307,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -620,6 +635,25 @@ class Context:
                                                          _ptr(prisms), int(O), _ptr(s_bounds_bar), _ptr(l_bounds_bar),
                                                          _ptr(prisms_bar), _stream(stream)), "btrapz_prism_bounds_vjp_device")
 
+    def prism_bounds_jvp_device(self, B, P, N, road, prisms, O, T, prisms_dot, s_bounds_dot, l_bounds_dot, stream=None):
+        """btrapz_prism_bounds_jvp_device: prisms_dot [T, B, P, 8]; s_bounds_dot / l_bounds_dot [T, B, O, N, 2] are
+        overwritten (either may be None: not wanted)."""
+        self._check(lib().btrapz_prism_bounds_jvp_device(self._h, int(B), int(P), int(N), C.byref(road) if road is not None else None,
+                                                         _ptr(prisms), int(O), int(T), _ptr(prisms_dot), _ptr(s_bounds_dot),
+                                                         _ptr(l_bounds_dot), _stream(stream)), "btrapz_prism_bounds_jvp_device")
+
+    def corridor_batch_jvp_device(self, variant, B, N, num_obs, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots,
+                                  s_ref, l_ref, seg_stride, T, tangents, seg_dot, ref_end_dot, dl_bounds_dot, stream=None):
+        """btrapz_corridor_batch_jvp_device: tangents = dict name -> device tensor with a leading axis T (KNOT_GRADS;
+        missing or None: zero); seg_dot [T, NUM_SEG_FIELDS, B, seg_stride], ref_end_dot [T, B, 2], dl_bounds_dot [T, B, 10]
+        are overwritten (any may be None: not wanted)."""
+        t = C.byref(CKnotTangents(*[_ptr(tangents.get(k)) for k in KNOT_GRADS])) if tangents is not None else None
+        self._check(lib().btrapz_corridor_batch_jvp_device(self._h, int(variant), int(B), int(N), int(num_obs), float(delta),
+                                                           _ptr(s_bounds), _ptr(l_bounds), _ptr(ds_bounds),
+                                                           _ptr(dl_bounds_knots), _ptr(s_ref), _ptr(l_ref), int(seg_stride),
+                                                           int(T), t, _ptr(seg_dot), _ptr(ref_end_dot), _ptr(dl_bounds_dot),
+                                                           _stream(stream)), "btrapz_corridor_batch_jvp_device")
+
     def prism_corridor_batch_device(self, variant, B, P, N, road, prisms, O, delta, ds_bounds, dl_bounds_knots, s_ref, l_ref,
                                     seg_stride, seg, seg_count, ref_end, dl_bounds, n_strips=None, stream=None):
         self._check(lib().btrapz_prism_corridor_batch_device(self._h, int(variant), B, P, N, C.byref(road), _ptr(prisms), O,
@@ -740,6 +774,56 @@ def corridor_vjp_host(variant, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_k
                                         int(seg_stride), *[_np_ptr(a) for a in bars], C.byref(g), C.byref(count))
     if rc != 0:
         raise BtrapzError("btrapz_corridor_vjp_host -> %d (invalid argument)" % rc)
+    return out, count.value
+
+
+def prism_bounds_jvp_host(prisms, N, O, prisms_dot, road=None, want=("s_bounds", "l_bounds")):
+    """btrapz_prism_bounds_jvp_host(): the forward-mode derivative of the prism stage on the host (no GPU).  prisms
+    [B, P, 8]; prisms_dot [T, B, P, 8] (entries 6, 7 and inactive slots are not read).  Returns (s_bounds_dot, l_bounds_dot),
+    each [T, B, O, N, 2] (None when not named in `want`)."""
+    prisms, prisms_dot = _np_f64(prisms), _np_f64(prisms_dot)
+    if prisms.ndim != 3 or prisms.shape[2] != 8:
+        raise ValueError("prisms must be [B, P, 8]")
+    B, P = prisms.shape[0], prisms.shape[1]
+    if prisms_dot is not None and (prisms_dot.ndim != 4 or prisms_dot.shape[1:] != (B, P, 8)):
+        raise ValueError("prisms_dot must be [T, B, P, 8]")
+    T = prisms_dot.shape[0] if prisms_dot is not None else 0
+    outs = [np.full((T, B, int(O), int(N), 2), np.nan) if k in want else None for k in ("s_bounds", "l_bounds")]
+    road = CRoad.reference() if road is None else road
+    rc = lib().btrapz_prism_bounds_jvp_host(B, P, int(N), C.byref(road), _np_ptr(prisms), int(O), int(T), _np_ptr(prisms_dot),
+                                            _np_ptr(outs[0]), _np_ptr(outs[1]))
+    if rc != 0:
+        raise BtrapzError("btrapz_prism_bounds_jvp_host -> %d (invalid argument)" % rc)
+    return outs[0], outs[1]
+
+
+def corridor_jvp_host(variant, delta, s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref, seg_stride, tangents,
+                      want=("seg", "ref_end", "dl_bounds")):
+    """btrapz_corridor_jvp_host(): the forward-mode derivative of the corridor stage for ONE candidate on the host (no
+    GPU).  Inputs as corridor_vjp_host; tangents: dict name -> array shaped like the input with a leading axis T (KNOT_GRADS;
+    missing or None: zero).  Returns (dict with "seg" [T, NUM_SEG_FIELDS, seg_stride], "ref_end" [T, 2], "dl_bounds" [T, 10]
+    as named in `want`, the forward's seg_count)."""
+    ins = [_np_f64(a) for a in (s_bounds, l_bounds, ds_bounds, dl_bounds_knots, s_ref, l_ref)]
+    sb = ins[0]
+    num_obs, N = (sb.shape[0], sb.shape[1]) if sb is not None else (0, 0)
+    unknown = set(tangents) - set(KNOT_GRADS)
+    if unknown:
+        raise ValueError("unknown tangents: %s" % sorted(unknown))
+    tan = {k: _np_f64(v) for k, v in tangents.items() if v is not None}
+    T = next(iter(tan.values())).shape[0] if tan else 0
+    shapes = dict(s_bounds=(num_obs, N, 2), l_bounds=(num_obs, N, 2), ds_bounds=(N, 2), dl_bounds_knots=(N, 2), s_ref=(N,), l_ref=(N,))
+    for k, v in tan.items():
+        if v.shape != (T,) + shapes[k]:
+            raise ValueError("tangent %r: shape %s, expected %s" % (k, v.shape, (T,) + shapes[k]))
+    out_shapes = dict(seg=(T, L.NUM_SEG_FIELDS, int(seg_stride)), ref_end=(T, 2), dl_bounds=(T, 10))
+    out = {k: np.full(out_shapes[k], np.nan) for k in want}
+    t = CKnotTangents(*[_np_ptr(tan.get(k)) for k in KNOT_GRADS])
+    count = C.c_int(-2)
+    rc = lib().btrapz_corridor_jvp_host(int(variant), int(N), int(num_obs), float(delta), *[_np_ptr(a) for a in ins],
+                                        int(seg_stride), int(T), C.byref(t), _np_ptr(out.get("seg")), _np_ptr(out.get("ref_end")),
+                                        _np_ptr(out.get("dl_bounds")), C.byref(count))
+    if rc != 0:
+        raise BtrapzError("btrapz_corridor_jvp_host -> %d (invalid argument)" % rc)
     return out, count.value
 
 

@@ -270,6 +270,54 @@ class BatchSolver:
         self.ctx.prism_bounds_vjp_device(B, P, N, road or CRoad.reference(), prisms, O, sbar, lbar, out, stream=self._stream())
         return out
 
+    def prism_bounds_jvp(self, prisms, N, O, prisms_dot, road=None):
+        """Forward-mode derivative of prism_bounds (btrapz_prism_bounds_jvp_device, one launch): prisms [B, P, 8] and T <= 32
+        directions prisms_dot [T, B, P, 8] (entries 6, 7 and inactive slots are not read) -> (s_bounds_dot, l_bounds_dot),
+        each [T, B, O, N, 2] = 16 T B O N bytes.  Decisions frozen, rounding straight-through (include/btrapz_hip_stage_jvp.h);
+        a scene with more than O strips gets zeros."""
+        prisms, prisms_dot = self._f64(prisms, detach=True), self._f64(prisms_dot, detach=True)
+        B, P = prisms.shape[0], prisms.shape[1]
+        if prisms_dot.dim() != 4 or tuple(prisms_dot.shape[1:]) != (B, P, 8):
+            raise ValueError("prisms_dot must be [T, B, P, 8] = [T, %d, %d, 8], not %s" % (B, P, tuple(prisms_dot.shape)))
+        T = prisms_dot.shape[0]
+        s_dot, l_dot = self._empty(T, B, O, N, 2), self._empty(T, B, O, N, 2)
+        self.ctx.prism_bounds_jvp_device(B, P, N, road or CRoad.reference(), prisms, O, T, prisms_dot, s_dot, l_dot,
+                                         stream=self._stream())
+        return s_dot, l_dot
+
+    def corridor_batch_jvp(self, kb_or_tensors, variant, tangents, delta=None, seg_stride=16):
+        """Forward-mode derivative of the device corridor stage (btrapz_corridor_batch_jvp_device).  kb_or_tensors: as in
+        corridor_batch_vjp.  tangents: a dict with any of "s_bounds", "l_bounds" [T, B, O, N, 2], "ds_bounds",
+        "dl_bounds_knots" [T, B, N, 2], "s_ref", "l_ref" [T, B, N]; a missing one is zero.  Returns {"seg": [T,
+        NUM_SEG_FIELDS, B, seg_stride], "ref_end": [T, B, 2], "dl_bounds": [T, B, 10]} -- the dict solve_jvp accepts."""
+        if hasattr(kb_or_tensors, "s_bounds"):
+            kb, up = kb_or_tensors, self._upload
+            ins = [up(kb.s_bounds), up(kb.l_bounds), up(kb.ds_bounds), up(kb.dl_bounds), up(kb.s_ref), up(kb.l_ref)]
+            delta = kb.delta if delta is None else delta
+        else:
+            ins = [self._f64(t, detach=True) for t in kb_or_tensors]
+            if delta is None:
+                raise ValueError("delta is needed with tensors")
+        B, O, N = ins[0].shape[0], ins[0].shape[1], ins[0].shape[2]
+        names = ("s_bounds", "l_bounds", "ds_bounds", "dl_bounds_knots", "s_ref", "l_ref")
+        unknown = set(tangents) - set(names)
+        if unknown:
+            raise ValueError("unknown tangents: %s" % sorted(unknown))
+        given = {k: v for k, v in tangents.items() if v is not None}
+        T = next(iter(given.values())).shape[0] if given else 0
+        tan = {}
+        for k, v in given.items():
+            shape = (T,) + tuple(ins[names.index(k)].shape)
+            if tuple(v.shape) != shape:
+                raise ValueError("tangent %r: shape %s, expected %s" % (k, tuple(v.shape), shape))
+            tan[k] = self._f64(v, detach=True)
+        seg_stride = int(seg_stride)
+        o = dict(seg=self._empty(max(T, 0), L.NUM_SEG_FIELDS, B, seg_stride), ref_end=self._empty(max(T, 0), B, 2),
+                 dl_bounds=self._empty(max(T, 0), B, 10))
+        self.ctx.corridor_batch_jvp_device(variant, B, N, O, delta, *ins, seg_stride, T, tan, o["seg"], o["ref_end"],
+                                           o["dl_bounds"], stream=self._stream())
+        return o   # (ins and tan were allocated on the launch's stream: the allocator hands their memory on in stream order)
+
     def corridor_batch_tensors(self, variant, N, delta, s_bounds, l_bounds, ds_bounds, dl_bounds, s_ref, l_ref, init,
                                seg_stride=16):
         """corridor_batch on device tensors (e.g. the output of prism_bounds): s_bounds, l_bounds [B, O, N, 2],
