@@ -253,6 +253,12 @@ __global__ void ipm_solve_lean_ordered_kernel(const KernelArgs a, const double *
 __global__ void ipm_solve_lean_capped_kernel(const KernelArgs a, const double *__restrict__ mqm);
 __global__ void ipm_solve_lean_capped_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm);
 __global__ void ipm_solve_lean_resume_kernel(const KernelArgs a, const double *__restrict__ mqm);
+// the lean two-launch solve as three launches (btrapz_lean_pipe.hip): one axis's capped launch, one grid of one axis's
+// resume wavefronts + the other axis's capped launch, one axis's resume launch; the lengths of both resume lists to the host
+__global__ void ipm_solve_lean_pipe_capped_kernel(const KernelArgs a, const double *__restrict__ mqm, int axis);
+__global__ void ipm_solve_lean_pipe_resume_kernel(const KernelArgs a, const double *__restrict__ mqm, int axis);
+__global__ void ipm_solve_lean_pipe_kernel(const KernelArgs a, const double *__restrict__ mqm, int n_resume, int resume_axis, int capped_axis);
+__global__ void pipe_counts_kernel(const int *tables, volatile int *host_counts);
 __global__ void ipm_solve_lean_warm_kernel(const KernelArgs a, const double *__restrict__ mqm);
 __global__ void ipm_solve_lean_warm_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm);
 // btrapz_solve_sets_device (btrapz_sets.hip, btrapz_kernels.hip): mqm = the per-set tables [n_sets][168]

@@ -15,6 +15,7 @@
 #include "btrapz_device.h"
 #include "corridor_jvp.h"
 #include "../../include/btrapz_hip_stage_jvp.h"
+#include "../../include/btrapz_hip_schedule.h"
 #include "prism_core.h"
 
 using namespace btrapz;
@@ -102,6 +103,15 @@ static inline const char *experiment_env(const char *name) {
 #define BTRAPZ_SUSP_PERCENT 15
 #endif
 #define BTRAPZ_SUSP_BYTES_MAX (1ull << 30)
+// The lean two-launch solve of a uniform batch in memory order may run as THREE launches, one axis's resume wavefronts
+// inside the other axis's capped launch (launch_pipelined below).  0: the schedule never runs and nothing
+// is remembered -- the two launches as they were (A/B builds: tools/build_variant.sh X -DBTRAPZ_PIPELINE=0).
+#ifndef BTRAPZ_PIPELINE
+#define BTRAPZ_PIPELINE 1
+#endif
+// ... chosen when the last finished solve of the same shape handed over at least this many times more problems of one
+// axis than of the other (a condition, not a tuned number: the bench families sit at 1 : 1 and at 10 000 : 1)
+#define BTRAPZ_PIPELINE_RATIO 4
 
 // Layout the lean kernels rely on (btrapz_lean_body.h reads the row limits of its axis as (&sh.acc_s[0])[2 axis + i],
 // (&sh.acc_s[0])[4 + 2 axis + i], and its arguments through the kernarg segment pointer: KernelArgs is the first parameter).
@@ -178,6 +188,14 @@ struct btrapz_ctx {
   Buf<int> d_susp_ints{bufs};       // [count, 3 pad] [bucket tables 2 x 198] [2B keys] [2B slots]
   int resident_waves = 1024;        // wavefronts the device holds at one per SIMD
   int last_form = -1;               // btrapz_last_solve_form
+  int last_launches = 0;            // btrapz_debug_solve_launches: solve-kernel launches of the last solve's main step
+  // Schedule of the lean two-launch solve (launch_pipelined): what the last FINISHED solve handed over per axis.  Every such
+  // solve leaves its two list lengths in h_pipe_counts (pinned host memory the device writes, stream-ordered) and records
+  // pipe_landed behind them; a later call takes them in only when a non-blocking query says they have landed.
+  int *h_pipe_counts = nullptr; hipEvent_t pipe_landed = nullptr; bool pipe_pending = false;
+  int pipe_pending_S = 0, pipe_pending_variant = -1;              // shape of the solve whose counts are on their way
+  int pipe_S = 0, pipe_variant = -1, pipe_count[2] = {0, 0};      // the counts that landed last, and their shape (pipe_S 0: none)
+  int schedule_mode = 0;            // btrapz_debug_set_schedule: 0 automatic, -1 never, 1 / 2 pipelined with s / l first
   // btrapz_solve_sets_device: the device view of every set and its M'QM table, cached by content (h_sets: what the tables
   // were built from); uploads go through two pinned staging buffers used in turn, the copy out of each marked by its event
   Buf<Shared> d_sets{bufs}; Buf<double> d_mqm_sets{bufs}; size_t sets_cap = 0;
@@ -262,6 +280,9 @@ BTRAPZ_EXPORT int btrapz_destroy(btrapz_ctx *c) {
     if (c->sets_copied[i]) (void)hipEventDestroy(c->sets_copied[i]);
   }
   if (c->ws_free) (void)hipEventDestroy(c->ws_free);
+  if (c->pipe_pending) (void)hipEventSynchronize(c->pipe_landed);   // (the device may still be writing h_pipe_counts)
+  if (c->pipe_landed) (void)hipEventDestroy(c->pipe_landed);
+  if (c->h_pipe_counts) (void)hipHostFree(c->h_pipe_counts);
   delete c;
   return BTRAPZ_OK;
 }
@@ -405,6 +426,15 @@ BTRAPZ_EXPORT int btrapz_debug_resume_keys(btrapz_ctx *c, int B, int *keys) {
   HIPCHK(c, hipMemcpy(keys, c->d_susp_ints + 400, sizeof(int) * 2 * B, hipMemcpyDeviceToHost));
   return BTRAPZ_OK;
 }
+// ... the schedule of the lean two-launch solves of uniform batches in memory order that follow (0: chosen from what
+// the last finished solve of the same shape handed over; -1: never three launches; 1 / 2: three launches with the s / l
+// axis first), and the number of solve-kernel launches the main step of the last solve made (1, 2 or 3)
+BTRAPZ_EXPORT int btrapz_debug_set_schedule(btrapz_ctx *c, int mode) {
+  if (!c || mode < -1 || mode > 2) return BTRAPZ_EINVAL;
+  c->schedule_mode = mode;
+  return BTRAPZ_OK;
+}
+BTRAPZ_EXPORT int btrapz_debug_solve_launches(const btrapz_ctx *c) { return c ? c->last_launches : -1; }
 
 int btrapz_launch_single(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_options *opt, int S, const double *in,
                          double *out, int max_points, int warm, void *stream_) {
@@ -703,6 +733,84 @@ static int launch_capped_and_resume(Solve &s, const Form &f, size_t slots) {
   const unsigned rblocks = 2u * (unsigned)(slots / (size_t)(64 / (S < 64 ? S : 64)) + 65);
   hipLaunchKernelGGL(f.lean_on ? ipm_solve_lean_resume_kernel : ipm_solve_resume_kernel, dim3(rblocks), dim3(64), 0, s.stream, p2, (const double *)c->d_mqm);
   c->last_form = f.lean_on ? 11 : 3;
+  c->last_launches = 2;
+  return BTRAPZ_OK;
+}
+
+// Which axis a lean two-launch solve of a uniform batch in memory order runs first when it runs as three launches; -1:
+// the two launches.  Automatic: the axis of which the last finished solve of this shape (S, variant) handed over at
+// least BTRAPZ_PIPELINE_RATIO times more problems than of the other -- the library cannot know the spread axis before
+// it solves, and consecutive batches of a planner are of one family.  Both schedules return the one-launch solve's bits:
+// what is remembered only moves time.
+static int pipeline_first_axis(btrapz_ctx *c, int S, int variant) {
+#if BTRAPZ_PIPELINE
+  if (c->schedule_mode != 0) return c->schedule_mode < 0 ? -1 : c->schedule_mode - 1;
+  if (c->pipe_pending) {   // never waited for: counts that have not landed leave the ones before them in place
+    if (hipEventQuery(c->pipe_landed) == hipSuccess) {
+      c->pipe_pending = false;
+      c->pipe_S = c->pipe_pending_S; c->pipe_variant = c->pipe_pending_variant;
+      c->pipe_count[0] = c->h_pipe_counts[0]; c->pipe_count[1] = c->h_pipe_counts[1];
+    } else {
+      (void)hipGetLastError();   // (hipErrorNotReady is an answer, not an error of this solve)
+    }
+  }
+  if (c->pipe_S != S || c->pipe_variant != variant) return -1;
+  const long long n0 = c->pipe_count[0], n1 = c->pipe_count[1];
+  if (n0 > 0 && n0 >= BTRAPZ_PIPELINE_RATIO * n1) return 0;
+  if (n1 > 0 && n1 >= BTRAPZ_PIPELINE_RATIO * n0) return 1;
+#endif
+  return -1;
+}
+
+// ... and what this solve handed over, for the next one: the two list lengths (cand_prefix[65] of each axis's table),
+// copied by the device behind the bucketing, and the event that says they have landed.  Failing to get the pinned
+// memory or the event only means that the schedule is never chosen automatically.
+static void pipeline_remember(Solve &s, const int *tables, int variant) {
+#if BTRAPZ_PIPELINE
+  btrapz_ctx *c = s.c;
+  if (!c->h_pipe_counts) {
+    if (hipHostMalloc((void **)&c->h_pipe_counts, sizeof(int) * 2, hipHostMallocDefault) != hipSuccess) { c->h_pipe_counts = nullptr; (void)hipGetLastError(); return; }
+    c->h_pipe_counts[0] = 0; c->h_pipe_counts[1] = 0;
+  }
+  if (!c->pipe_landed && hipEventCreateWithFlags(&c->pipe_landed, hipEventDisableTiming) != hipSuccess) { c->pipe_landed = nullptr; (void)hipGetLastError(); return; }
+  hipLaunchKernelGGL(pipe_counts_kernel, dim3(1), dim3(64), 0, s.stream, tables, c->h_pipe_counts);
+  if (hipEventRecord(c->pipe_landed, s.stream) != hipSuccess) { (void)hipGetLastError(); c->pipe_pending = false; c->pipe_S = 0; return; }
+  c->pipe_pending = true; c->pipe_pending_S = s.S; c->pipe_pending_variant = variant;
+#else
+  (void)s; (void)tables; (void)variant;
+#endif
+}
+
+// The lean two-launch solve of a uniform batch in memory order as three launches on the one stream:
+//   1. the capped launch of axis a0 alone, then the bucketing of ITS hand-over lists;
+//   2. one grid: the resume wavefronts of a0 (dispatched first: their long dependent chains run beside full-width work)
+//      and, behind them, the capped launch of the other axis a1;
+//   3. the bucketing of a1's lists and a1's resume launch.
+// Every dependency is a kernel boundary; inside launch 2 no wavefront waits for another (btrapz_lean_pipe.hip).  One
+// KernelArgs serves all three; one memset, one slot counter: the slots a1 takes lie behind those a0's resume part reads.
+static int launch_pipelined(Solve &s, const Form &f, size_t slots, int a0) {
+  btrapz_ctx *c = s.c; const int B = s.B, S = s.S, a1 = 1 - a0;
+  int *count = c->d_susp_ints, *tables = count + 4, *keys = tables + 2 * 198, *slot_of = keys + 2 * (size_t)B;
+  HIPCHK(c, hipMemsetAsync(count, 0, sizeof(int) * (400 + 2 * (size_t)B), s.stream));
+  int *lists = c->d_rescue + 2 * (size_t)B;
+  KernelArgs p = s.a;
+  p.cap_iter = f.cap_iter; p.cap_alone = BTRAPZ_CAP_ALONE; p.cap_hi = f.cap_iter + BTRAPZ_CAP_HI; p.cap_score = BTRAPZ_CAP_SCORE; p.susp_cap = (int)slots; p.susp_state = c->d_susp_state; p.susp_count = count;
+  p.susp_slot = slot_of; p.susp_key = keys;
+  // (what the resume parts read and the memory-order capped parts do not: the lists and their tables, [2][..] by axis)
+  p.order = lists; p.seg_count = nullptr; p.cand_prefix = tables; p.wave_prefix = tables + 66; p.bucket_S = S;
+  const int gpw = 64 / S;
+  const unsigned cblocks = (unsigned)((B + gpw - 1) / gpw);            // one axis of the batch
+  const unsigned rblocks = (unsigned)(slots / (size_t)gpw + 65);       // one axis's lists at most: every class wastes less than one wavefront
+  auto bucket = [&](int ax) {
+    launch_bucket_lists(s.stream, 1, B, S, keys + (size_t)ax * B, tables + ax * 198, lists + (size_t)ax * B, nullptr, nullptr, nullptr, -S);
+  };
+  hipLaunchKernelGGL(ipm_solve_lean_pipe_capped_kernel, dim3(cblocks), dim3(64), 0, s.stream, p, (const double *)c->d_mqm, a0);
+  bucket(a0);
+  hipLaunchKernelGGL(ipm_solve_lean_pipe_kernel, dim3(rblocks + cblocks), dim3(64), 0, s.stream, p, (const double *)c->d_mqm, (int)rblocks, a0, a1);
+  bucket(a1);
+  hipLaunchKernelGGL(ipm_solve_lean_pipe_resume_kernel, dim3(rblocks), dim3(64), 0, s.stream, p, (const double *)c->d_mqm, a1);
+  c->last_form = 11;
+  c->last_launches = 3;
   return BTRAPZ_OK;
 }
 
@@ -710,6 +818,7 @@ static int launch_capped_and_resume(Solve &s, const Form &f, size_t slots) {
 static int solve_main_launch(Solve &s, Form &f) {
   btrapz_ctx *c = s.c; KernelArgs &a = s.a;
   const int B = s.B, S = s.S;
+  c->last_launches = 1;
   FormQuery q{};
   q.B = B; q.S = S; q.ragged = s.seg_count != nullptr; q.warm_kernel = s.warm_kernel; q.ordered = a.order != nullptr; q.compact = s.compact;
   q.elastic = s.elastic; q.max_iter = a.max_iter; q.unc_start = a.unc_start; q.resident_waves = c->resident_waves; q.blocks = s.blocks;
@@ -723,7 +832,13 @@ static int solve_main_launch(Solve &s, Form &f) {
   size_t slots = 0;   // (q.cap_iter > 0: asked for by the caller; the automatic choice falls back to one launch without the workspace)
   if (f.capped) TRY(capped_workspace(s, q.cap_iter > 0, &slots));
   if (slots) {
-    TRY(launch_capped_and_resume(s, f, slots));
+    // (three launches: the lean form on uniform batches in memory order; not the ordered path -- ragged batches, the
+    //  pre-pass -- whose capped part needs a.order and the prefix tables for its own lists, nor the packed form)
+    const bool pipe_ok = f.lean_on && !s.seg_count && !a.order;
+    const int first_axis = pipe_ok ? pipeline_first_axis(c, S, a.sh.variant) : -1;
+    if (first_axis >= 0) TRY(launch_pipelined(s, f, slots, first_axis));
+    else TRY(launch_capped_and_resume(s, f, slots));
+    if (pipe_ok) pipeline_remember(s, c->d_susp_ints + 4, a.sh.variant);
   } else if (f.long_form) {
     c->last_form = 2;
     hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, s.stream, a, (const double *)c->d_mqm);
@@ -1012,6 +1127,7 @@ BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *s
   }
   hipStream_t stream = (hipStream_t)stream_;
   TRY(ws_open(c, stream));
+  c->last_launches = 1;   // (the sets solve never runs the two launches)
   TRY(ensure_axis_ws(c, 2 * (size_t)B));
   TRY(sets_tables(c, sets, n_sets, stream));
   KernelArgs a;

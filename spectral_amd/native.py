@@ -229,6 +229,13 @@ PROTOTYPES_STAGE_JVP = {
 }
 EXPORTS_STAGE_JVP = tuple(PROTOTYPES_STAGE_JVP)
 
+# Every function of include/btrapz_hip_schedule.h, the same way (tests/test_abi_schedule.py holds it to that header).
+PROTOTYPES_SCHEDULE = {
+    "btrapz_debug_set_schedule": (_i, [_vp, _i]),
+    "btrapz_debug_solve_launches": (_i, [_vp]),
+}
+EXPORTS_SCHEDULE = tuple(PROTOTYPES_SCHEDULE)
+
 
 def _ptr(t):
     """Device tensor -> its address as a c_void_p; None -> None (a NULL argument or struct field), always.  Keeps nothing
@@ -272,7 +279,7 @@ def kernel_source_hash():
     the solve kernel's code (profiles/*.json carry it; bench.py refuses profiles of other kernel sources)."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("btrapz_kernels.hip", "btrapz_lean.hip", "btrapz_lean_warm.hip", "btrapz_lean_body.h", "btrapz_ipm.h", "btrapz_device.h", "Makefile",
+    for f in ("btrapz_kernels.hip", "btrapz_lean.hip", "btrapz_lean_warm.hip", "btrapz_lean_pipe.hip", "btrapz_lean_body.h", "btrapz_ipm.h", "btrapz_device.h", "Makefile",
               os.path.join("..", "..", "include", "btrapz_hip.h")):
         with open(os.path.join(CSRC_DIR, f), "rb") as fh:
             h.update(fh.read())
@@ -307,7 +314,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -576,6 +583,14 @@ class Context:
         k = np.zeros((2, B), dtype=np.int32)
         self._check(lib().btrapz_debug_resume_keys(self._h, B, _np_ptr(k)), "btrapz_debug_resume_keys")
         return k
+
+    def debug_set_schedule(self, mode):
+        """btrapz_debug_set_schedule: 0 automatic, -1 never three launches, 1 / 2 three launches with the s / l axis first."""
+        self._check(lib().btrapz_debug_set_schedule(self._h, int(mode)), "btrapz_debug_set_schedule")
+
+    def debug_solve_launches(self):
+        """Solve-kernel launches of the main step of the last batched solve: 1, 2 or 3."""
+        return int(lib().btrapz_debug_solve_launches(self._h))
 
     def debug_mqm_tables(self, shared):
         sh = CShared.from_shared(shared)

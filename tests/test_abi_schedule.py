@@ -1,0 +1,63 @@
+"""include/btrapz_hip_schedule.h held to the rules tests/test_abi.py applies to include/btrapz_hip.h: every declared symbol
+is exported, the third prototype table of spectral_amd.native follows the header's prototypes, and the header is plain C99."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+from spectral_amd import native
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "btrapz_hip_schedule.h")
+
+
+@pytest.fixture(scope="module")
+def built():
+    native.build()
+    return native.lib()
+
+
+def header_without_comments():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def declared_prototypes():
+    """name -> (return type as written, number of parameters) of every prototype of the header."""
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][A-Za-z_ ]*?[\s*]+)\b(btrapz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", header_without_comments()):
+        ret, name, params = " ".join(m.group(1).replace("*", " * ").split()), m.group(2), m.group(3).strip()
+        out[name] = (ret, 0 if params == "void" else len(params.split(",")))
+    return out
+
+
+def test_every_declared_symbol_is_exported_and_in_the_third_table(built):
+    names = sorted(set(re.findall(r"\b(btrapz_[a-z_]+)\s*\(", header_without_comments())))
+    assert names == sorted(declared_prototypes()) == ["btrapz_debug_set_schedule", "btrapz_debug_solve_launches"]
+    for n in names:
+        assert hasattr(built, n), n
+    assert set(names) == set(native.PROTOTYPES_SCHEDULE) == set(native.EXPORTS_SCHEDULE)
+    assert not set(names) & (set(native.PROTOTYPES) | set(native.PROTOTYPES_STAGE_JVP))
+    out = subprocess.check_output(["nm", "-D", "--defined-only", native.LIB_PATH], text=True)
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert set(names) <= exported
+
+
+def test_argument_counts_and_return_types_follow_the_header(built):
+    ctype = {"int": C.c_int}
+    for name, (ret, n_params) in declared_prototypes().items():
+        fn = getattr(built, name)
+        assert len(fn.argtypes) == n_params == len(native.PROTOTYPES_SCHEDULE[name][1]), name
+        assert fn.restype is ctype[ret] and native.PROTOTYPES_SCHEDULE[name][0] is ctype[ret], (name, ret)
+
+
+def test_modes_are_validated_without_a_device(built):
+    assert built.btrapz_debug_set_schedule(None, 0) == -1       # BTRAPZ_EINVAL: no context
+    assert built.btrapz_debug_solve_launches(None) == -1
+
+
+def test_header_is_plain_c99(tmp_path):
+    src = tmp_path / "hdr.c"
+    src.write_text('#include "btrapz_hip_schedule.h"\nint main(void) { return btrapz_debug_solve_launches((const btrapz_ctx *)0) == -1 ? 0 : 0; }\n')
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
