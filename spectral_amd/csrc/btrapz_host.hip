@@ -13,6 +13,7 @@
 #include <cstddef>
 #include <type_traits>
 #include "btrapz_device.h"
+#include "btrapz_select.h"
 #include "corridor_jvp.h"
 #include "../../include/btrapz_hip_stage_jvp.h"
 #include "../../include/btrapz_hip_schedule.h"
@@ -172,6 +173,7 @@ struct btrapz_ctx {
   // ordered behind each other with this event (recorded after every sequence, waited for when the stream changes: ws_open).
   hipEvent_t ws_free = nullptr; hipStream_t ws_stream = nullptr; bool ws_used = false;
   Buf<double> d_argmin_cost{bufs}; Buf<long long> d_argmin_idx{bufs};   // partial arg-mins (one capacity, idx allocated last)
+  Buf<double> d_topk_cost{bufs}; Buf<long long> d_topk_idx{bufs};       // partial K-best lists (btrapz_select.hip), the same way
   // rescue pass (btrapz_options.elastic): keys [2][B], per-axis candidate lists [2][B], bucket tables [2][198]
   Buf<int> d_rescue{bufs};
   Buf<int> d_rescue_meta{bufs};
@@ -234,6 +236,18 @@ static int ws_close(btrapz_ctx *c, hipStream_t stream) {
 
 int btrapz_ctx_device(const btrapz_ctx *c) { return c ? c->device : 0; }
 void btrapz_ctx_set_error(btrapz_ctx *c, const char *what) { if (c) c->err = what; }
+// btrapz_select.h: the workspace of the K-best selection's two-launch path (btrapz_select.hip)
+int btrapz_ctx_select_workspace(btrapz_ctx *c, size_t entries, void *stream_, double **cost, long long **idx) {
+  if (entries > c->d_topk_idx.cap()) {
+    release_all(c->d_topk_cost, c->d_topk_idx);
+    GROW(c, d_topk_cost, sizeof(double) * entries);
+    GROW(c, d_topk_idx, sizeof(long long) * entries);
+  }
+  TRY(ws_wait(c, (hipStream_t)stream_));
+  *cost = c->d_topk_cost.ptr(); *idx = c->d_topk_idx.ptr();
+  return BTRAPZ_OK;
+}
+int btrapz_ctx_workspace_close(btrapz_ctx *c, void *stream_) { return ws_close(c, (hipStream_t)stream_); }
 
 BTRAPZ_EXPORT int btrapz_device_count(void) {
   int n = 0;

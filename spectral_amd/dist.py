@@ -147,6 +147,63 @@ def global_argmin_with_winner(best_cost, best_idx, local_ctrl, group=None, ctx=N
     return out_c, out_i, ctrl
 
 
+def global_topk(best_cost, best_idx, group=None, ctx=None, force_collective=False, local_rows=None):
+    """The K-wide form of global_argmin / global_argmin_with_winner.  best_cost [n, K] float64, best_idx [n, K] int64: this
+    rank's K best of every group (BatchSolver.topk on its shard with its index_base: global indices, -1 / +inf = no
+    candidate), in any order within a list.  Returns (cost [n, K], idx [n, K]): the K best over all ranks in the arg-min's
+    total order -- cost ascending, equal costs -> lowest global index --, slots nobody fills -1 / +inf; identical on every
+    rank.  Entries with index -1 or a cost that is NaN / +inf take no part.
+
+    The layout contract is global_argmin's: list g of EVERY rank belongs to the same group, spread over the ranks; groups
+    that live on one rank need no collective.  One all_gather of n x K x 16 bytes per rank, the costs as bit patterns
+    beside the int64 indices.  With ctx (a spectral_amd.native.Context) and device tensors the merge is one launch of the
+    library (btrapz_topk_pairs_device) on torch's current stream; otherwise torch ops with the same result.
+
+    With local_rows [n, K, P] float64 -- e.g. the control points of this rank's K best, any finite filler where best_idx
+    is -1 -- the rows travel in the SAME all_gather and a third result rows [n, K, P] holds every winner's row, taken from
+    the rank whose list carries its index; rows of -1 slots are NaN."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    assert best_cost.shape == best_idx.shape and best_cost.dim() == 2
+    n, K = best_cost.shape
+    assert local_rows is None or (local_rows.dim() == 3 and tuple(local_rows.shape[:2]) == (n, K))
+    if world == 1 and not (force_collective and dist.is_initialized()):
+        if local_rows is None:
+            return best_cost, best_idx
+        rows = local_rows.clone()
+        rows[best_idx < 0] = float("nan")
+        return best_cost, best_idx, rows
+    parts = [best_cost.to(torch.float64).contiguous().view(torch.int64)[..., None], best_idx.to(torch.int64)[..., None]]
+    if local_rows is not None:
+        parts.append(local_rows.to(torch.float64).contiguous().view(torch.int64))
+    rec = torch.cat(parts, dim=-1).contiguous()                               # [n][K][2 (+ P)] int64
+    dev = rec.device
+    allr = _all_gather_records(rec, group)                                    # [world][n][K][2 (+ P)]
+    pairs = allr[..., :2].contiguous()
+    cost = pairs[..., 0].contiguous().view(torch.float64).permute(1, 0, 2).reshape(n, world * K)
+    idx = pairs[..., 1].permute(1, 0, 2).reshape(n, world * K)                # list g of all ranks, rank-major
+    if ctx is not None and pairs.is_cuda:
+        out_c = torch.empty(n, K, dtype=torch.float64, device=dev); out_i = torch.empty(n, K, dtype=torch.int64, device=dev)
+        ctx.topk_pairs_device(world, n, K, pairs, out_c, out_i, stream=torch.cuda.current_stream(dev).cuda_stream)
+    else:
+        takes = (idx >= 0) & (cost < float("inf"))                            # (NaN < inf is false)
+        big = torch.iinfo(torch.int64).max
+        key_c = torch.where(takes, cost, torch.full_like(cost, float("inf")))
+        key_i = torch.where(takes, idx, torch.full_like(idx, big))
+        by_idx = torch.argsort(key_i, dim=1, stable=True)                     # lexicographic: index, then (stable) cost
+        order = by_idx.gather(1, torch.argsort(key_c.gather(1, by_idx), dim=1, stable=True))[:, :K]
+        out_c = key_c.gather(1, order)
+        out_i = torch.where(takes.gather(1, order), idx.gather(1, order), torch.full_like(order, -1))
+    if local_rows is None:
+        return out_c, out_i
+    # the owner of a winner: the (one) entry of the gathered lists that carries its index
+    at = ((idx[:, None, :] == out_i[:, :, None]) & (out_i >= 0)[:, :, None]).to(torch.int64).argmax(dim=2)   # [n][K]
+    P = local_rows.shape[2]
+    rows = allr[..., 2:].permute(1, 0, 2, 3).reshape(n, world * K, P).gather(1, at[:, :, None].expand(n, K, P))
+    rows = rows.contiguous().view(torch.float64)
+    rows = torch.where((out_i >= 0)[:, :, None], rows, torch.full_like(rows, float("nan")))
+    return out_c, out_i, rows
+
+
 def fetch_winner(ctrl, win_idx, per, index_base, group=None):
     """The winner's control points from its owner by ONE broadcast.  ctrl [B_local][P]: this rank's solved
     control points; win_idx: the winner's GLOBAL index as a python int (the caller has it on the host), -1 = none;

@@ -236,6 +236,15 @@ PROTOTYPES_SCHEDULE = {
 }
 EXPORTS_SCHEDULE = tuple(PROTOTYPES_SCHEDULE)
 
+# Every function of include/btrapz_hip_select.h, the same way (tests/test_abi_select.py holds it to that header).
+PROTOTYPES_SELECT = {
+    "btrapz_topk_device": (_i, [_vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
+    "btrapz_topk_pairs_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_gather_rows_device": (_i, [_vp, _i, _vp, _ll, _i, _i, _vp, _vp, _vp]),
+}
+EXPORTS_SELECT = tuple(PROTOTYPES_SELECT)
+MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
+
 
 def _ptr(t):
     """Device tensor -> its address as a c_void_p; None -> None (a NULL argument or struct field), always.  Keeps nothing
@@ -314,7 +323,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -691,6 +700,21 @@ class Context:
     def argmin_pairs_device(self, world, n, pairs, best_cost, best_idx, stream=None):
         self._check(lib().btrapz_argmin_pairs_device(self._h, int(world), int(n), _ptr(pairs), _ptr(best_cost), _ptr(best_idx),
                                                      _stream(stream)), "btrapz_argmin_pairs_device")
+
+    def topk_device(self, B, group, K, index_base, cost, best_idx, best_cost, stream=None):
+        """btrapz_topk_device: best_idx / best_cost [B // group, K], the K best of every group in the arg-min's order."""
+        self._check(lib().btrapz_topk_device(self._h, int(B), int(group), int(K), int(index_base), _ptr(cost), _ptr(best_idx),
+                                             _ptr(best_cost), _stream(stream)), "btrapz_topk_device")
+
+    def topk_pairs_device(self, world, n, K, pairs, best_cost, best_idx, stream=None):
+        """btrapz_topk_pairs_device: pairs [world, n, K, 2] int64 (cost bits, global index or -1) -> [n, K]."""
+        self._check(lib().btrapz_topk_pairs_device(self._h, int(world), int(n), int(K), _ptr(pairs), _ptr(best_cost),
+                                                   _ptr(best_idx), _stream(stream)), "btrapz_topk_pairs_device")
+
+    def gather_rows_device(self, n, idx, index_base, B, row_doubles, src, rows, stream=None):
+        """btrapz_gather_rows_device: rows[j] = src[idx[j] - index_base], NaN rows for -1 and for indices outside the shard."""
+        self._check(lib().btrapz_gather_rows_device(self._h, int(n), _ptr(idx), int(index_base), int(B), int(row_doubles),
+                                                    _ptr(src), _ptr(rows), _stream(stream)), "btrapz_gather_rows_device")
 
     def sample_device(self, B, S, delta, seg, init, ctrl, sel, max_points, out, npoints, stream=None):
         self._check(lib().btrapz_sample_device(self._h, B, S, float(delta), _ptr(seg), _ptr(init), _ptr(ctrl),

@@ -452,6 +452,23 @@ class BatchSolver:
         self.ctx.argmin_device(B, group, index_base, cost, best_idx, best_cost, stream=self._stream())
         return best_idx, best_cost
 
+    def topk(self, cost, K, group=None, index_base=0):
+        """The K best candidates of every contiguous group (default: the whole batch) in argmin's order -- cost ascending,
+        equal costs -> lowest index -- by btrapz_topk_device.  Returns (best_idx [G, K] int64, best_cost [G, K]) device
+        tensors; slots beyond the candidates that take part (cost < +inf) hold -1 / +inf.  K == 1 is argmin.  The same on
+        every call and every rank: unlike torch.topk the order among equal costs is fixed.
+
+        To sample or evaluate the winners pass `(best_idx - index_base).flatten()` as `sel` to sample / eval_states (put
+        -1 back where best_idx is -1: such a selection yields 0 points); a winner that is refused afterwards is followed
+        by the next column, without another solve."""
+        B = cost.numel()
+        group = B if group is None else group
+        if group < 1 or B % group != 0:
+            raise ValueError("topk: group %r does not divide the %d costs" % (group, B))
+        best_idx, best_cost = self._empty(B // group, K, dtype=torch.int64), self._empty(B // group, K)
+        self.ctx.topk_device(B, group, K, index_base, self._f64(cost), best_idx, best_cost, stream=self._stream())
+        return best_idx, best_cost
+
     def sample(self, dbatch, ctrl, sel, delta):
         """Bernstein sampling (solve_3d.cc:1279-1392) of the selected candidates of a DeviceBatch or a ragged record
         (btrapz_sample_device / btrapz_sample_ragged_device) -> (out [nsel, 6, max_points], npoints [nsel])."""
