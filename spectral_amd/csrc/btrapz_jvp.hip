@@ -29,6 +29,7 @@ namespace btrapz {
 #define JVP_RHO 1e6
 #define HSYM(H, i, j) ((i) <= (j) ? H[SYM(i, j)] : H[SYM(j, i)])
 #define JVP_PASSES 3
+#define JVP_SLACK_ACTIVE 3.1622776601683794e-4   // vjp_kernel's VJP_SLACK_ACTIVE: rows whose kept multiplier is no number
 
 // rows this kernel keeps: those of the solve (rows_kept<false>: 1-5, 7-10, 12-17)
 #define JVP_ROWS(r) static_for<15>([&](auto r##_c) { constexpr int r = row_id<false>(decltype(r##_c)::value); constexpr int ri_ = state_index<false>(r); (void)ri_;
@@ -185,7 +186,8 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
       const double gc = row_dot<r>(c, t);
       const double ll = act ? a.lam[lam_e + (size_t)r * lam_row] : 0.0, lu = act ? a.lam[lam_e + (size_t)(18 + r) * lam_row] : 0.0;
       const double lo = VLO(r), up = VUP(r);
-      const bool al = ll > gc - lo && !(fabs(lo) >= BTRAPZ_FAR), au = lu > up - gc && !(fabs(up) >= BTRAPZ_FAR);
+      const bool al = (fabs(ll) < 1e300 ? ll > gc - lo : gc - lo < JVP_SLACK_ACTIVE) && !(fabs(lo) >= BTRAPZ_FAR);
+      const bool au = (fabs(lu) < 1e300 ? lu > up - gc : up - gc < JVP_SLACK_ACTIVE) && !(fabs(up) >= BTRAPZ_FAR);
       side[ri_] = (act && (al || au)) ? ((al && au) ? (ll >= lu ? -1 : 1) : (al ? -1 : 1)) : 0;
       rho[ri_] = side[ri_] != 0 ? JVP_RHO * pscale / (r < 6 ? t2 : r < 11 ? 50.0 : r < 15 ? 2400.0 : 72000.0) : 0.0;
       w[ri_] = 0.0;

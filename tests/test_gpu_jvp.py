@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from grad_edge_cases import SHAPES, _dev, _directions, _fmt, _identity, _per_tangent_ratios, _ragged, _solve
 from jvp_reference import KEYS, Tangent
 from spectral_amd import diff, layout as L, synth, tune
 from spectral_amd.native import MAX_TANGENTS, BtrapzError
@@ -23,61 +24,11 @@ FAMILIES = {
     "scenario_1": lambda S, seed: synth.make_scenario1_batch(B, S, 0, seed=seed),
     "cuboid": lambda S, seed: synth.make_scenario1_batch(B, S, 1, seed=seed),
 }
-SHAPES = lambda T, B_, S: dict(seg=(T, L.NUM_SEG_FIELDS, B_, S), init=(T, B_, 6), ref_end=(T, B_, 2), dl_bounds=(T, B_, 10),
-                               shared=(T, B_, 20))
-
 
 @pytest.fixture(scope="module")
 def solver():
     from spectral_amd.solver import BatchSolver
     return BatchSolver(0)
-
-
-def _solve(solver, batch, sh, lean=0):
-    db = solver.upload(batch)
-    d = solver.device
-    o = solver.solve(db, sh, keep_multipliers=True, lean=lean, out={
-        "ctrl": torch.zeros((batch.B, 12 * batch.S), dtype=torch.float64, device=d),
-        "cost": torch.empty(batch.B, dtype=torch.float64, device=d),
-        "status": torch.empty(batch.B, dtype=torch.int32, device=d),
-        "iters": torch.empty(batch.B, dtype=torch.int32, device=d)})
-    return db, o
-
-
-def _directions(rng, T, B_, S, keys=KEYS):
-    """Dense random tangents [T, ...] in the named arrays (numpy); field 0 of seg random too: it must be ignored."""
-    return {k: rng.standard_normal(SHAPES(T, B_, S)[k]) for k in keys}
-
-
-def _dev(solver, tan):
-    return {k: torch.tensor(v, device=solver.device) for k, v in tan.items()}
-
-
-def _ragged(solver, batch, W, counts):
-    """The batch in a ragged record of stride W with the given segment counts (candidates keep their first count segments)."""
-    d = solver.device
-    seg = np.zeros((L.NUM_SEG_FIELDS, batch.B, W)); seg[:, :, :batch.S] = batch.seg
-    return dict(B=batch.B, seg_stride=W, seg=torch.tensor(seg, device=d), seg_count=torch.tensor(counts, dtype=torch.int32, device=d),
-                init=torch.tensor(batch.init, device=d), ref_end=torch.tensor(batch.ref_end, device=d),
-                dl_bounds=torch.tensor(batch.dl_bounds, device=d))
-
-
-FLOOR = 1e-3
-
-
-def _per_tangent_ratios(cd, cs, ref_x, ref_c):
-    """Errors of ctrl_dot [T, 12 S] and cost_dot [T] of one candidate, each tangent relative to ITS OWN reference's largest
-    entry.  A tangent whose reference is (nearly) 0 is measured against FLOOR = 1e-3 of the candidate's largest tangent.
-    The floor comes from the yardstick's own error: its least-squares solve of the singular KKT matrix differs from a
-    null-space solve of the same system by up to 7e-8 of the largest tangent (64 segments, CPU only), so a reference
-    of exactly 0 comes back as 1e-10 to 1e-8, and 1e-4 x 1e-3 = 1e-7 of the largest tangent is what it can certify."""
-    nx = np.abs(ref_x).max(1); nc = np.abs(ref_c)
-    sx = np.maximum(nx, max(FLOOR * nx.max(), 1e-300)); sc = np.maximum(nc, max(FLOOR * nc.max(), 1e-300))
-    return np.abs(cd - ref_x).max(1) / sx, np.abs(cs - ref_c) / sc
-
-
-def _fmt(v):
-    return "[" + " ".join("%.1e" % x for x in np.atleast_1d(v)) + "]"
 
 
 @pytest.mark.parametrize("family", list(FAMILIES))
@@ -146,35 +97,6 @@ def test_jvp_against_the_yardstick(solver, family, S):
     # (ref_end moves nothing where d_ref is 0; no l-axis velocity row is active in these families: dl_bounds has a test of
     # its own, test_dl_bounds_tangent_on_active_rows)
     assert (seen[[0, 1, 2, 5]] > 0).all(), seen
-
-
-def _identity(solver, rec, sets, o, set_index, S, T=3, seed=0, keys=KEYS):
-    rng = np.random.default_rng(seed)
-    Bn = rec["B"] if isinstance(rec, dict) else rec.B
-    d = solver.device
-    tan = _directions(rng, T, Bn, S)
-    for k in KEYS:
-        if k not in keys:
-            tan[k][:] = 0.0
-    xbar = rng.standard_normal((Bn, 12 * S)); cbar = rng.standard_normal(Bn)
-    g = solver.solve_vjp(rec, sets, o, torch.tensor(xbar, device=d), torch.tensor(cbar, device=d), set_index=set_index)
-    j = solver.solve_jvp(rec, sets, o, _dev(solver, tan), set_index=set_index)
-    torch.cuda.synchronize()
-    g = {k: v.cpu().numpy() for k, v in g.items()}
-    cd, cs = j["ctrl"].cpu().numpy(), j["cost"].cpu().numpy()
-    st = o["status"].cpu().numpy()
-    solved = (st == 1) | (st == 2)
-    assert solved.sum() >= Bn // 2
-    worst = 0.0
-    for t in range(T):
-        lhs = (xbar * cd[t]).sum(1) + cbar * cs[t]
-        mag = (np.abs(xbar) * np.abs(cd[t])).sum(1) + np.abs(cbar) * np.abs(cs[t])
-        rhs = (np.moveaxis(g["seg"], 1, 0) * np.moveaxis(tan["seg"][t], 1, 0)).sum((1, 2))
-        for k in ("init", "ref_end", "dl_bounds", "shared"):
-            rhs = rhs + (g[k] * tan[k][t]).sum(1)
-        ratio = np.abs(lhs - rhs)[solved] / np.maximum(mag[solved], 1e-300)
-        worst = max(worst, float(ratio.max()))
-    return worst
 
 
 def test_adjoint_identity_against_the_vjp(solver):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from grad_edge_cases import _cand, _close, _solve_and_vjp
 from spectral_amd import diff, layout as L, synth
 from spectral_amd.native import BtrapzError
 from vjp_reference import reference_vjp
@@ -29,30 +30,9 @@ def solver():
     return BatchSolver(0)
 
 
-def _solve_and_vjp(solver, batch, sh, xbar, cbar, lean=0):
-    db = solver.upload(batch)
-    o = solver.solve(db, sh, keep_multipliers=True, lean=lean, out={
-        "ctrl": torch.zeros((batch.B, 12 * batch.S), dtype=torch.float64, device=solver.device),
-        "cost": torch.empty(batch.B, dtype=torch.float64, device=solver.device),
-        "status": torch.empty(batch.B, dtype=torch.int32, device=solver.device),
-        "iters": torch.empty(batch.B, dtype=torch.int32, device=solver.device)})
-    g = solver.solve_vjp(db, sh, o, xbar, cbar)
-    torch.cuda.synchronize()
-    return o, {k: v.cpu().numpy() for k, v in g.items()}
-
-
 def _copy(batch):
     return L.Batch(B=batch.B, S=batch.S, seg=batch.seg.copy(), init=batch.init.copy(), ref_end=batch.ref_end.copy(),
                    dl_bounds=batch.dl_bounds.copy())
-
-
-def _cand(g, b):
-    return dict(seg=g["seg"][:, b], init=g["init"][b], ref_end=g["ref_end"][b], dl_bounds=g["dl_bounds"][b],
-                shared=g["shared"][b])
-
-
-def _close(a, r, tol=1e-4):
-    return np.abs(a - r).max() <= tol * max(np.abs(r).max(), np.abs(a).max(), 1e-300)
 
 
 @pytest.mark.parametrize("family", list(FAMILIES))

@@ -48,7 +48,7 @@ class Adjoint:
         self.batch, self.sh, self.S = batch, sh, batch.S
         qp, P, A, q, l, u = dense(batch, sh)
         x, y, info = qp.solve_exact()
-        self.status = int(info.status_val) if hasattr(info, "status_val") else 1
+        self.status = int(info.status)   # (oracle.Info: OSQP's status_val vocabulary, 1 = solved)
         self.P, self.A, self.q, self.l, self.u, self.x, self.y = P, A, q, l, u, x, y
         self.cbar = float(cbar)
         xb = np.asarray(xbar, dtype=float) + self.cbar * (P @ x + q)
