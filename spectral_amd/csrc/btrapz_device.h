@@ -259,6 +259,12 @@ __global__ void ipm_solve_lean_pipe_capped_kernel(const KernelArgs a, const doub
 __global__ void ipm_solve_lean_pipe_resume_kernel(const KernelArgs a, const double *__restrict__ mqm, int axis);
 __global__ void ipm_solve_lean_pipe_kernel(const KernelArgs a, const double *__restrict__ mqm, int n_resume, int resume_axis, int capped_axis);
 __global__ void pipe_counts_kernel(const int *tables, volatile int *host_counts);
+// ... and with one axis quiet (btrapz_lean_quiet.hip): that axis through the plain body -- in a launch of its own, or in one
+// grid behind the other axis's resume wavefronts --, and the count it would have handed over, estimated from axis_iters
+__global__ void ipm_solve_lean_quiet_plain_kernel(const KernelArgs a, const double *__restrict__ mqm, int axis);
+__global__ void ipm_solve_lean_quiet_kernel(const KernelArgs a, const double *__restrict__ mqm, int n_resume, int resume_axis, int plain_axis);
+__global__ void quiet_counts_kernel(const int *__restrict__ axis_iters, int B, int gpw, int quiet_axis, int cap_iter, int cap_hi,
+                                    const int *tables, int *acc, volatile int *host_counts);
 __global__ void ipm_solve_lean_warm_kernel(const KernelArgs a, const double *__restrict__ mqm);
 __global__ void ipm_solve_lean_warm_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm);
 // btrapz_solve_sets_device (btrapz_sets.hip, btrapz_kernels.hip): mqm = the per-set tables [n_sets][168]

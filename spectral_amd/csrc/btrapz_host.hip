@@ -113,6 +113,10 @@ static inline const char *experiment_env(const char *name) {
 // ... chosen when the last finished solve of the same shape handed over at least this many times more problems of one
 // axis than of the other (a condition, not a tuned number: the bench families sit at 1 : 1 and at 10 000 : 1)
 #define BTRAPZ_PIPELINE_RATIO 4
+// ... and with the other axis QUIET -- solved uncapped, in the grid of the first axis's resume wavefronts
+// (launch_quiet_axis below) -- when it handed over at least this many times more (again a condition: the families whose
+// lateral axis is quiet sit at 1 000 : 1 and beyond -- 11 149 : 1, 1 067 : 0, 5 073 : 0, 15 410 : 1)
+#define BTRAPZ_QUIET_RATIO 256
 
 // Layout the lean kernels rely on (btrapz_lean_body.h reads the row limits of its axis as (&sh.acc_s[0])[2 axis + i],
 // (&sh.acc_s[0])[4 + 2 axis + i], and its arguments through the kernarg segment pointer: KernelArgs is the first parameter).
@@ -197,7 +201,7 @@ struct btrapz_ctx {
   int *h_pipe_counts = nullptr; hipEvent_t pipe_landed = nullptr; bool pipe_pending = false;
   int pipe_pending_S = 0, pipe_pending_variant = -1;              // shape of the solve whose counts are on their way
   int pipe_S = 0, pipe_variant = -1, pipe_count[2] = {0, 0};      // the counts that landed last, and their shape (pipe_S 0: none)
-  int schedule_mode = 0;            // btrapz_debug_set_schedule: 0 automatic, -1 never, 1 / 2 pipelined with s / l first
+  int schedule_mode = 0;            // btrapz_debug_set_schedule: 0 automatic, -1 never, 1 / 2 pipelined with s / l first, 3 / 4 s / l first and the other axis quiet
   // btrapz_solve_sets_device: the device view of every set and its M'QM table, cached by content (h_sets: what the tables
   // were built from); uploads go through two pinned staging buffers used in turn, the copy out of each marked by its event
   Buf<Shared> d_sets{bufs}; Buf<double> d_mqm_sets{bufs}; size_t sets_cap = 0;
@@ -442,9 +446,10 @@ BTRAPZ_EXPORT int btrapz_debug_resume_keys(btrapz_ctx *c, int B, int *keys) {
 }
 // ... the schedule of the lean two-launch solves of uniform batches in memory order that follow (0: chosen from what
 // the last finished solve of the same shape handed over; -1: never three launches; 1 / 2: three launches with the s / l
-// axis first), and the number of solve-kernel launches the main step of the last solve made (1, 2 or 3)
+// axis first; 3 / 4: the s / l axis first and the other one quiet, uncapped), and the number of solve-kernel launches the
+// main step of the last solve made (1, 2 or 3)
 BTRAPZ_EXPORT int btrapz_debug_set_schedule(btrapz_ctx *c, int mode) {
-  if (!c || mode < -1 || mode > 2) return BTRAPZ_EINVAL;
+  if (!c || mode < -1 || mode > 4) return BTRAPZ_EINVAL;
   c->schedule_mode = mode;
   return BTRAPZ_OK;
 }
@@ -751,12 +756,14 @@ static int launch_capped_and_resume(Solve &s, const Form &f, size_t slots) {
   return BTRAPZ_OK;
 }
 
-// Which axis a lean two-launch solve of a uniform batch in memory order runs first when it runs as three launches; -1:
-// the two launches.  Automatic: the axis of which the last finished solve of this shape (S, variant) handed over at
-// least BTRAPZ_PIPELINE_RATIO times more problems than of the other -- the library cannot know the spread axis before
-// it solves, and consecutive batches of a planner are of one family.  Both schedules return the one-launch solve's bits:
-// what is remembered only moves time.
-static int pipeline_first_axis(btrapz_ctx *c, int S, int variant) {
+// The schedule of a lean two-launch solve of a uniform batch in memory order.  -1: the two launches; 0 / 1: three
+// launches with the s / l axis first (launch_pipelined); 2 / 3: the s / l axis first and the other one quiet
+// (launch_quiet_axis).  Automatic: from what the last finished solve of this shape (S, variant) handed over per axis -- at
+// least BTRAPZ_QUIET_RATIO times more problems of one axis than of the other: that axis first, the other quiet; at least
+// BTRAPZ_PIPELINE_RATIO times more: that axis first -- the library cannot know the spread axis before it solves, and
+// consecutive batches of a planner are of one family.  Every schedule returns the one-launch solve's bits: what is
+// remembered only moves time.
+static int pipeline_schedule(btrapz_ctx *c, int S, int variant) {
 #if BTRAPZ_PIPELINE
   if (c->schedule_mode != 0) return c->schedule_mode < 0 ? -1 : c->schedule_mode - 1;
   if (c->pipe_pending) {   // never waited for: counts that have not landed leave the ones before them in place
@@ -770,6 +777,8 @@ static int pipeline_first_axis(btrapz_ctx *c, int S, int variant) {
   }
   if (c->pipe_S != S || c->pipe_variant != variant) return -1;
   const long long n0 = c->pipe_count[0], n1 = c->pipe_count[1];
+  if (n0 > 0 && n0 >= BTRAPZ_QUIET_RATIO * n1) return 2;
+  if (n1 > 0 && n1 >= BTRAPZ_QUIET_RATIO * n0) return 3;
   if (n0 > 0 && n0 >= BTRAPZ_PIPELINE_RATIO * n1) return 0;
   if (n1 > 0 && n1 >= BTRAPZ_PIPELINE_RATIO * n0) return 1;
 #endif
@@ -777,21 +786,32 @@ static int pipeline_first_axis(btrapz_ctx *c, int S, int variant) {
 }
 
 // ... and what this solve handed over, for the next one: the two list lengths (cand_prefix[65] of each axis's table),
-// copied by the device behind the bucketing, and the event that says they have landed.  Failing to get the pinned
-// memory or the event only means that the schedule is never chosen automatically.
-static void pipeline_remember(Solve &s, const int *tables, int variant) {
+// copied by the device behind the bucketing, and the event that says they have landed.  An axis that ran quiet
+// (quiet_axis 0 / 1; -1: none) has no list: its entry is the estimate of quiet_counts_kernel (btrapz_lean_quiet.hip) of
+// what the cap would have made it hand over -- or the library would never learn that the axis has started to talk.
+// Failing to get the pinned memory or the event only means that the schedule is never chosen automatically.
+static void pipeline_remember(Solve &s, int *count, int variant, int quiet_axis, int cap_iter) {
 #if BTRAPZ_PIPELINE
   btrapz_ctx *c = s.c;
+  const int *tables = count + 4;
   if (!c->h_pipe_counts) {
     if (hipHostMalloc((void **)&c->h_pipe_counts, sizeof(int) * 2, hipHostMallocDefault) != hipSuccess) { c->h_pipe_counts = nullptr; (void)hipGetLastError(); return; }
     c->h_pipe_counts[0] = 0; c->h_pipe_counts[1] = 0;
   }
   if (!c->pipe_landed && hipEventCreateWithFlags(&c->pipe_landed, hipEventDisableTiming) != hipSuccess) { c->pipe_landed = nullptr; (void)hipGetLastError(); return; }
-  hipLaunchKernelGGL(pipe_counts_kernel, dim3(1), dim3(64), 0, s.stream, tables, c->h_pipe_counts);
+  if (quiet_axis < 0) {
+    hipLaunchKernelGGL(pipe_counts_kernel, dim3(1), dim3(64), 0, s.stream, tables, c->h_pipe_counts);
+  } else {
+    // (one thread per memory-order wavefront; count[1], count[2]: the pad behind the slot counter, zeroed with it)
+    const int gpw = 64 / s.S;
+    const unsigned waves = (unsigned)((s.B + gpw - 1) / gpw);
+    hipLaunchKernelGGL(quiet_counts_kernel, dim3((waves + 255u) / 256u), dim3(256), 0, s.stream, (const int *)s.a.axis_iters, s.B, gpw, quiet_axis,
+                       cap_iter, cap_iter + BTRAPZ_CAP_HI, tables, count + 1, c->h_pipe_counts);
+  }
   if (hipEventRecord(c->pipe_landed, s.stream) != hipSuccess) { (void)hipGetLastError(); c->pipe_pending = false; c->pipe_S = 0; return; }
   c->pipe_pending = true; c->pipe_pending_S = s.S; c->pipe_pending_variant = variant;
 #else
-  (void)s; (void)tables; (void)variant;
+  (void)s; (void)count; (void)variant; (void)quiet_axis; (void)cap_iter;
 #endif
 }
 
@@ -828,6 +848,32 @@ static int launch_pipelined(Solve &s, const Form &f, size_t slots, int a0) {
   return BTRAPZ_OK;
 }
 
+// ... and with axis a1 quiet (btrapz_lean_quiet.hip): a1 hands nothing over, so it needs no cap, no lists
+// and no resume launch -- it goes through the plain one-launch body, behind a0's resume wavefronts:
+//   1. the capped launch of axis a0 alone, then the bucketing of its hand-over lists (as in launch_pipelined);
+//   2. one grid: the resume wavefronts of a0 and, behind them, axis a1 of the batch in memory order, to the end.
+// Two solve kernels and one bucketing triple; a1's keys stay as the memset left them.  btrapz_debug_solve_launches
+// answers 3 as for launch_pipelined: it is what tells an axis-first schedule from the two launches of both axes.
+static int launch_quiet_axis(Solve &s, const Form &f, size_t slots, int a0) {
+  btrapz_ctx *c = s.c; const int B = s.B, S = s.S, a1 = 1 - a0;
+  int *count = c->d_susp_ints, *tables = count + 4, *keys = tables + 2 * 198, *slot_of = keys + 2 * (size_t)B;
+  HIPCHK(c, hipMemsetAsync(count, 0, sizeof(int) * (400 + 2 * (size_t)B), s.stream));
+  int *lists = c->d_rescue + 2 * (size_t)B;
+  KernelArgs p = s.a;
+  p.cap_iter = f.cap_iter; p.cap_alone = BTRAPZ_CAP_ALONE; p.cap_hi = f.cap_iter + BTRAPZ_CAP_HI; p.cap_score = BTRAPZ_CAP_SCORE; p.susp_cap = (int)slots; p.susp_state = c->d_susp_state; p.susp_count = count;
+  p.susp_slot = slot_of; p.susp_key = keys;
+  p.order = lists; p.seg_count = nullptr; p.cand_prefix = tables; p.wave_prefix = tables + 66; p.bucket_S = S;
+  const int gpw = 64 / S;
+  const unsigned cblocks = (unsigned)((B + gpw - 1) / gpw);
+  const unsigned rblocks = (unsigned)(slots / (size_t)gpw + 65);
+  hipLaunchKernelGGL(ipm_solve_lean_pipe_capped_kernel, dim3(cblocks), dim3(64), 0, s.stream, p, (const double *)c->d_mqm, a0);
+  launch_bucket_lists(s.stream, 1, B, S, keys + (size_t)a0 * B, tables + a0 * 198, lists + (size_t)a0 * B, nullptr, nullptr, nullptr, -S);
+  hipLaunchKernelGGL(ipm_solve_lean_quiet_kernel, dim3(rblocks + cblocks), dim3(64), 0, s.stream, p, (const double *)c->d_mqm, (int)rblocks, a0, a1);
+  c->last_form = 11;
+  c->last_launches = 3;
+  return BTRAPZ_OK;
+}
+
 // Step: the main launch -- the form is chosen, the two-launch solve gets its workspace, the kernels go out.
 static int solve_main_launch(Solve &s, Form &f) {
   btrapz_ctx *c = s.c; KernelArgs &a = s.a;
@@ -849,10 +895,11 @@ static int solve_main_launch(Solve &s, Form &f) {
     // (three launches: the lean form on uniform batches in memory order; not the ordered path -- ragged batches, the
     //  pre-pass -- whose capped part needs a.order and the prefix tables for its own lists, nor the packed form)
     const bool pipe_ok = f.lean_on && !s.seg_count && !a.order;
-    const int first_axis = pipe_ok ? pipeline_first_axis(c, S, a.sh.variant) : -1;
-    if (first_axis >= 0) TRY(launch_pipelined(s, f, slots, first_axis));
+    const int schedule = pipe_ok ? pipeline_schedule(c, S, a.sh.variant) : -1;
+    if (schedule >= 2) TRY(launch_quiet_axis(s, f, slots, schedule - 2));
+    else if (schedule >= 0) TRY(launch_pipelined(s, f, slots, schedule));
     else TRY(launch_capped_and_resume(s, f, slots));
-    if (pipe_ok) pipeline_remember(s, c->d_susp_ints + 4, a.sh.variant);
+    if (pipe_ok) pipeline_remember(s, c->d_susp_ints, a.sh.variant, schedule >= 2 ? 3 - schedule : -1, f.cap_iter);
   } else if (f.long_form) {
     c->last_form = 2;
     hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, s.stream, a, (const double *)c->d_mqm);

@@ -288,7 +288,7 @@ def kernel_source_hash():
     the solve kernel's code (profiles/*.json carry it; bench.py refuses profiles of other kernel sources)."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("btrapz_kernels.hip", "btrapz_lean.hip", "btrapz_lean_warm.hip", "btrapz_lean_pipe.hip", "btrapz_lean_body.h", "btrapz_ipm.h", "btrapz_device.h", "Makefile",
+    for f in ("btrapz_kernels.hip", "btrapz_lean.hip", "btrapz_lean_warm.hip", "btrapz_lean_pipe.hip", "btrapz_lean_quiet.hip", "btrapz_lean_body.h", "btrapz_ipm.h", "btrapz_device.h", "Makefile",
               os.path.join("..", "..", "include", "btrapz_hip.h")):
         with open(os.path.join(CSRC_DIR, f), "rb") as fh:
             h.update(fh.read())
@@ -594,7 +594,8 @@ class Context:
         return k
 
     def debug_set_schedule(self, mode):
-        """btrapz_debug_set_schedule: 0 automatic, -1 never three launches, 1 / 2 three launches with the s / l axis first."""
+        """btrapz_debug_set_schedule: 0 automatic, -1 never three launches, 1 / 2 three launches with the s / l axis first,
+        3 / 4 the s / l axis first and the other axis quiet (uncapped, behind the first axis's resume wavefronts)."""
         self._check(lib().btrapz_debug_set_schedule(self._h, int(mode)), "btrapz_debug_set_schedule")
 
     def debug_solve_launches(self):

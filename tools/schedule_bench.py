@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The schedules of the lean two-launch solve (btrapz_debug_set_schedule: -1 the two launches, 1 / 2 three launches with
-the s / l axis first, 0 the library's choice once it has seen a solve) on the bench batches, all in memory order
+the s / l axis first, 3 / 4 the s / l axis first and the other axis quiet, 0 the library's choice once it has seen a
+solve) on the bench batches, all in memory order
 (compact = -1): time of the whole solve call by HIP events, hand-over counts per axis, and whether the results are the
 one-launch solve's bit for bit.  One JSON object on stdout.
 
@@ -42,7 +43,7 @@ def main(argv=None):
         ref = {k: o[k].cpu().numpy().copy() for k in ("ctrl", "cost", "status", "iters")}
         ok = ref["status"] > 0
         rec = {}
-        for mode in (-1, 1, 2, 0):
+        for mode in (-1, 1, 2, 3, 4, 0):
             solver.ctx.debug_set_schedule(mode)
             for _ in range(2):
                 o = solver.solve(db, sh, cap_iter=a.cap, **kw)
@@ -63,7 +64,7 @@ def main(argv=None):
                 "bit_identical": bool(np.array_equal(ref["status"], res["status"]) and np.array_equal(ref["iters"], res["iters"]) and
                                       np.array_equal(ref["ctrl"][ok], res["ctrl"][ok]) and np.array_equal(ref["cost"], res["cost"]))}
         solver.ctx.debug_set_schedule(0)
-        for m in ("mode_1", "mode_2", "mode_0"):
+        for m in ("mode_1", "mode_2", "mode_3", "mode_4", "mode_0"):
             rec[m]["ratio"] = rec[m]["solve_ms"] / rec["mode_-1"]["solve_ms"]
         out[label] = rec
     print(json.dumps(out))
