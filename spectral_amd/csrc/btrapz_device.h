@@ -111,6 +111,20 @@ struct JvpArgs {
 };
 __global__ void jvp_kernel(const JvpArgs a);
 
+// btrapz_check_rows_device (btrapz_check.hip)
+struct CheckArgs {
+  int B, seg_stride;        // groups of min(seg_stride, 64) lanes; beyond 64 slots one candidate per wavefront
+  int unit;                 // btrapz_row_check.unit
+  const int *seg_count;     // [B] or null
+  const Shared *sets;       // [n_sets] device view of the parameter sets
+  int n_sets;
+  const int *set_index;     // [B] or null (set 0)
+  const double *mqm;        // [n_sets][168] M'QM tables of the sets
+  const double *seg, *init, *ref_end, *dl_bounds, *ctrl;
+  double *margin; int *worst; double *eq_res, *obj;   // any may be null
+};
+__global__ void check_rows_kernel(const CheckArgs a);
+
 // btrapz_traj_cost_device / btrapz_traj_cost_vjp_device (btrapz_acost.hip)
 struct AcostArgs {
   int B, seg_stride;

@@ -17,6 +17,7 @@
 #include "corridor_jvp.h"
 #include "../../include/btrapz_hip_stage_jvp.h"
 #include "../../include/btrapz_hip_schedule.h"
+#include "../../include/btrapz_hip_check.h"
 #include "prism_core.h"
 
 using namespace btrapz;
@@ -1316,6 +1317,67 @@ BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *se
   const unsigned gpw = 64u / (unsigned)seg_stride;
   const unsigned blocks = (unsigned)(((size_t)B + gpw - 1) / gpw);
   hipLaunchKernelGGL(jvp_kernel, dim3(blocks), dim3(128), 0, stream, a);
+  HIPCHK(c, hipGetLastError());
+  return ws_close(c, stream);
+}
+
+// The audit of given control points against every row of their QP (btrapz_check_rows_device, include/btrapz_hip_check.h):
+// one launch of check_rows_kernel (btrapz_check.hip) -- groups of seg_stride lanes as vjp_kernel lays them out, one
+// candidate per wavefront beyond 64 slots.  The sets' device view and M'QM tables are the context's; nothing else is kept.
+BTRAPZ_EXPORT int btrapz_check_rows_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                        int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                        const double *ref_end, const double *dl_bounds, const double *ctrl,
+                                        const btrapz_row_check *out, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (!out || out->struct_size != sizeof(btrapz_row_check)) {
+    c->err = "invalid argument: check_rows needs out, with out->struct_size = sizeof(btrapz_row_check)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!out->margin && !out->worst && !out->eq_res && !out->obj) {
+    c->err = "invalid argument: check_rows needs at least one output (all NULL)";
+    return BTRAPZ_EINVAL;
+  }
+  if (out->unit != 0 && out->unit != 1) {
+    c->err = "invalid argument: check_rows: unit is 0 (the rows' own units) or 1 (divided by the rows' norms)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!sets_in_range(sets, n_sets)) {
+    c->err = "invalid argument: 1 <= n_sets <= BTRAPZ_MAX_SETS and sets non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride < 1 || seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: check_rows: 1 <= seg_stride <= BTRAPZ_MAX_SEGMENTS_LONG";
+    return BTRAPZ_EINVAL;
+  }
+  if (B < 0) {
+    c->err = "invalid argument: check_rows: B >= 0";
+    return BTRAPZ_EINVAL;
+  }
+  for (int g = 1; g < n_sets; g++)
+    if (sets[g].variant != sets[0].variant) {
+      c->err = "invalid argument: check_rows: every parameter set must have the same variant";
+      return BTRAPZ_EINVAL;
+    }
+  if (B == 0) return BTRAPZ_OK;
+  if (!seg || !init || !ref_end || !dl_bounds || !ctrl) {
+    c->err = "invalid argument: check_rows: the batch arrays and ctrl non-null";
+    return BTRAPZ_EINVAL;
+  }
+  if (((size_t)ctrl & 15) != 0) {
+    c->err = "invalid argument: check_rows: ctrl must be 16-byte aligned";
+    return BTRAPZ_EINVAL;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRY(ws_open(c, stream));
+  TRY(sets_tables(c, sets, n_sets, stream));
+  CheckArgs a;
+  a.B = B; a.seg_stride = seg_stride; a.unit = out->unit; a.seg_count = seg_count;
+  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets;
+  a.seg = seg; a.init = init; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl;
+  a.margin = out->margin; a.worst = out->worst; a.eq_res = out->eq_res; a.obj = out->obj;
+  const unsigned gpw = seg_stride < 64 ? 64u / (unsigned)seg_stride : 1u;
+  const unsigned blocks = (unsigned)(((size_t)B + gpw - 1) / gpw);
+  hipLaunchKernelGGL(check_rows_kernel, dim3(blocks), dim3(64), 0, stream, a);
   HIPCHK(c, hipGetLastError());
   return ws_close(c, stream);
 }

@@ -69,6 +69,12 @@ class CTangents(C.Structure):
 MAX_TANGENTS = 32   # BTRAPZ_MAX_TANGENTS
 
 
+class CRowCheck(C.Structure):
+    """btrapz_row_check (include/btrapz_hip_check.h): the unit and the output device pointers of btrapz_check_rows_device."""
+    _fields_ = [("struct_size", C.c_size_t), ("unit", C.c_int), ("margin", C.c_void_p), ("worst", C.c_void_p),
+                ("eq_res", C.c_void_p), ("obj", C.c_void_p)]
+
+
 class CKnotGrads(C.Structure):
     """btrapz_knot_grads (include/btrapz_hip.h): pointers of the gradient arrays of btrapz_corridor_batch_vjp_device
     (device) / btrapz_corridor_vjp_host (host)."""
@@ -243,6 +249,12 @@ PROTOTYPES_SELECT = {
     "btrapz_gather_rows_device": (_i, [_vp, _i, _vp, _ll, _i, _i, _vp, _vp, _vp]),
 }
 EXPORTS_SELECT = tuple(PROTOTYPES_SELECT)
+
+# Every function of include/btrapz_hip_check.h, the same way (tests/test_abi_check.py holds it to that header).
+PROTOTYPES_CHECK = {
+    "btrapz_check_rows_device": (_i, [_vp, _sh, _i, _vp, _i, _i] + _ragged + [_vp, C.POINTER(CRowCheck), _vp]),
+}
+EXPORTS_CHECK = tuple(PROTOTYPES_CHECK)
 MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
 
 
@@ -323,7 +335,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -546,6 +558,17 @@ class Context:
                                                   _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
                                                   _ptr(ctrl), _ptr(lam), _ptr(status), int(T), C.byref(tan), _ptr(ctrl_dot),
                                                   _ptr(cost_dot), _stream(stream)), "btrapz_solve_jvp_device")
+
+    def check_rows_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, unit=0,
+                          margin=None, worst=None, eq_res=None, obj=None, stream=None):
+        """btrapz_check_rows_device: the audit of ctrl [B, 12 seg_stride] against every row of the record's QPs.  sets /
+        set_index / seg_count as in solve_vjp_device; unit 0 = the rows' own units, 1 = divided by the rows' norms; margin
+        [B, 2, 4] / worst [B, 2, 4] int32 / eq_res [B, 2, 2] / obj [B] device tensors are overwritten (None: not wanted)."""
+        out = CRowCheck(C.sizeof(CRowCheck), int(unit), _ptr(margin), _ptr(worst), _ptr(eq_res), _ptr(obj))
+        self._check(lib().btrapz_check_rows_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), int(B),
+                                                   int(seg_stride), _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end),
+                                                   _ptr(dl_bounds), _ptr(ctrl), C.byref(out), _stream(stream)),
+                    "btrapz_check_rows_device")
 
     def traj_cost_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ctrl, status, N, s_ref, l_ref,
                          ref_stride, a_cost, n_points=None, stream=None):

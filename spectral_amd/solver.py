@@ -444,6 +444,42 @@ class BatchSolver:
                                       s_ref_bar=g["s_ref"], l_ref_bar=g["l_ref"], stream=self._stream())
         return g
 
+    # ---- the audit of control points against the rows of their QP --------------------------------
+    def check_rows(self, rec_or_dbatch, shared_or_sets, ctrl, set_index=None, unit=0, want=("margin", "worst", "eq_res", "obj")):
+        """Audit of ctrl [B, 12 S] against every row of the QP the record states for each candidate
+        (btrapz_check_rows_device, one launch, nothing solved).  rec_or_dbatch: a DeviceBatch or a ragged record;
+        shared_or_sets: its layout.Shared, or the list of sets with set_index (int32 device tensor [B]); unit 0: every row
+        in its own unit, 1: divided by the row's norm (the unit of elastic_tol).  Returns a dict of the device tensors named
+        in `want`: "margin" [B, 2, 4] (s axis, l axis; position, velocity, acceleration, jerk rows: the smallest distance
+        to a bound, negative = violated, +inf = no bound), "worst" [B, 2, 4] int32 (the row 18 k + r that attains it, -1:
+        none), "eq_res" [B, 2, 2] (largest residual of the initial-state rows, of the continuity rows), "obj" [B] (the
+        solve's cost at ctrl).  A candidate that cannot be audited -- a non-finite control point, a segment count or set
+        out of range, a duration <= 0 -- has margins -inf, worst -1, eq_res +inf, obj +inf."""
+        r = self._record(rec_or_dbatch)
+        B, S = r.B, r.S
+        unknown = set(want) - {"margin", "worst", "eq_res", "obj"}
+        if unknown:
+            raise ValueError("unknown outputs: %s" % sorted(unknown))
+        if set_index is not None:
+            _check_index(set_index, B)
+        ctrl = self._f64(ctrl, detach=True)
+        if tuple(ctrl.shape) != (B, 12 * S):
+            raise ValueError("ctrl must be [B, 12 S] = %s, not %s" % ((B, 12 * S), tuple(ctrl.shape)))
+        shapes = dict(margin=((B, 2, 4), torch.float64), worst=((B, 2, 4), torch.int32), eq_res=((B, 2, 2), torch.float64),
+                      obj=((B,), torch.float64))
+        o = {k: self._empty(*shapes[k][0], dtype=shapes[k][1]) for k in want}
+        self.ctx.check_rows_device(B, S, _sets_of(shared_or_sets), set_index, r.seg, r.seg_count, r.init, r.ref_end,
+                                   r.dl_bounds, ctrl, unit=unit, stream=self._stream(), **o)
+        return o
+
+    @staticmethod
+    def admissible(check, tol_rows, tol_eq):
+        """A check_rows result (with "margin" and "eq_res") -> [B] bool mask: all eight margins >= -tol_rows and all four
+        equality residuals <= tol_eq.  Written as comparisons that a NaN fails: NaN and the -inf / +inf of a candidate
+        that cannot be audited come out False."""
+        m, e = check["margin"], check["eq_res"]
+        return (m >= -float(tol_rows)).reshape(m.shape[0], -1).all(dim=1) & (e <= float(tol_eq)).reshape(e.shape[0], -1).all(dim=1)
+
     def argmin(self, cost, group=None, index_base=0):
         """Arg-min of cost over contiguous groups (default: the whole batch). Device tensors."""
         B = cost.numel()
