@@ -161,7 +161,9 @@ enum {
  * beyond 64 a candidate is solved by a workgroup of several wavefronts (same method, same result, much slower per
  * segment -- the reference has no limit, its bundled inputs have at most 14).  The rescue pass (btrapz_options.elastic
  * = 1) follows up to BTRAPZ_MAX_SEGMENTS_LONG_RESCUE segments (three wavefronts: a fourth's LDS does not fit);
- * ragged batches, warm starts and elastic = 2 stay at BTRAPZ_MAX_SEGMENTS. */
+ * warm ragged batches, warm starts and elastic = 2 stay at BTRAPZ_MAX_SEGMENTS in the entry points of this header.  Warm
+ * starts and kept multipliers of candidates of 65..256 segments, uniform or ragged: btrapz_solve_long_warm_device,
+ * btrapz_hip_long.h. */
 #define BTRAPZ_MAX_SEGMENTS_LONG 256
 #define BTRAPZ_MAX_SEGMENTS_LONG_RESCUE 192
 
@@ -300,7 +302,8 @@ int btrapz_rescue_violations_device(btrapz_ctx *ctx, int B, double *viol, void *
  * 0 packed (floor(64/S) candidates per wavefront), 1 split (btrapz_options.split), 2 long (65..256 segments),
  * 3 capped first launch + resume launch (btrapz_options.cap_iter), 4 candidate queue (experiment builds); -1 none yet.
  * + 8 when the launch(es) ran the two-wavefronts-per-SIMD form (btrapz_options.lean); + 16 when the long form solved the
- * candidates of more than 64 segments of a ragged batch beside it. */
+ * candidates of more than 64 segments of a ragged batch beside it; 16 alone: the warm-start instantiation of the long form
+ * on a uniform batch (btrapz_solve_long_warm_device, btrapz_hip_long.h). */
 int btrapz_last_solve_form(const btrapz_ctx *ctx);
 
 /* Arg-min of cost over contiguous groups of `group` candidates (B % group == 0).

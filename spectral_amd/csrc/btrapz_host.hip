@@ -18,6 +18,7 @@
 #include "../../include/btrapz_hip_stage_jvp.h"
 #include "../../include/btrapz_hip_schedule.h"
 #include "../../include/btrapz_hip_check.h"
+#include "../../include/btrapz_hip_long.h"
 #include "prism_core.h"
 
 using namespace btrapz;
@@ -616,6 +617,7 @@ struct Solve {
   int B, S; const int *seg_count;   // S: segments of a uniform batch (seg_count == nullptr), slot stride of a ragged one
   KernelArgs a;
   int elastic; bool compact, warm_kernel;
+  bool long_warm;                   // btrapz_solve_long_warm_device: candidates of 65..256 segments take ipm_solve_long_warm_kernel
   unsigned blocks;                  // wavefronts of the one-launch packed / lean form
 };
 
@@ -885,7 +887,7 @@ static int solve_main_launch(Solve &s, Form &f) {
   q.elastic = s.elastic; q.max_iter = a.max_iter; q.unc_start = a.unc_start; q.resident_waves = c->resident_waves; q.blocks = s.blocks;
   solve_requests(s.opt, q);
   f = choose_form(q);
-  if (f.long_form && (a.order || s.warm_kernel || s.elastic == 2 || (s.elastic == 1 && S > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE))) {
+  if (f.long_form && (a.order || (s.warm_kernel && !s.long_warm) || s.elastic == 2 || (s.elastic == 1 && S > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE))) {
     c->err = "more than 64 segments: uniform cold solve only, rescue pass (elastic = 1) up to 192 segments";
     return BTRAPZ_EINVAL;
   }
@@ -901,6 +903,9 @@ static int solve_main_launch(Solve &s, Form &f) {
     else if (schedule >= 0) TRY(launch_pipelined(s, f, slots, schedule));
     else TRY(launch_capped_and_resume(s, f, slots));
     if (pipe_ok) pipeline_remember(s, c->d_susp_ints, a.sh.variant, schedule >= 2 ? 3 - schedule : -1, f.cap_iter);
+  } else if (f.long_form && s.long_warm) {
+    c->last_form = 16;   // (the warm instantiation, whatever the start: it is the one that writes lam_out)
+    hipLaunchKernelGGL(ipm_solve_long_warm_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, s.stream, a, (const double *)c->d_mqm);
   } else if (f.long_form) {
     c->last_form = 2;
     hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, s.stream, a, (const double *)c->d_mqm);
@@ -989,7 +994,8 @@ static int solve_rescue_pass(Solve &s, bool long_form) {
 // pre-pass and ordering -> main launch -> rescue pass -> long candidates of a ragged batch -> finalise and close.
 static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_options *opt, const btrapz_warm *warm,
                         int B, int S, const int *seg_count, const double *seg, const double *init, const double *ref_end,
-                        const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters, void *stream_) {
+                        const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters, void *stream_,
+                        bool long_warm = false) {
   if (!c) return BTRAPZ_EINVAL;
   if (!sh || B < 1 || S < 1 || (!seg_count && S > BTRAPZ_MAX_SEGMENTS_LONG) || !seg || !init || !ref_end || !dl_bounds ||
       !ctrl || !cost || !status) {
@@ -998,7 +1004,7 @@ static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_opt
   }
   if (!options_ok(c, opt)) return BTRAPZ_EINVAL;
   Solve s;
-  s.c = c; s.stream = (hipStream_t)stream_; s.opt = opt; s.B = B; s.S = S; s.seg_count = seg_count;
+  s.c = c; s.stream = (hipStream_t)stream_; s.opt = opt; s.B = B; s.S = S; s.seg_count = seg_count; s.long_warm = long_warm;
   TRY(ws_open(c, s.stream));
   TRY(ensure_axis_ws(c, 2 * (size_t)B));
   TRY(solve_weights_table(c, sh, s.stream));
@@ -1018,9 +1024,11 @@ static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_opt
   Form f;
   TRY(solve_main_launch(s, f));
   if (s.elastic) TRY(solve_rescue_pass(s, f.long_form));
-  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && !s.warm_kernel && s.elastic == 0) {
+  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && (!s.warm_kernel || long_warm) && s.elastic == 0) {
+    // (a warm ragged solve leaves its long candidates at BTRAPZ_NO_CORRIDOR; btrapz_solve_long_warm_device solves them warm)
+    auto kernel = s.warm_kernel ? ipm_solve_long_warm_kernel : ipm_solve_long_kernel;
     auto launch = [&](const KernelArgs &l, unsigned n, int segs) {
-      hipLaunchKernelGGL(ipm_solve_long_kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, s.stream, l, (const double *)c->d_mqm);
+      hipLaunchKernelGGL(kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, s.stream, l, (const double *)c->d_mqm);
     };
     TRY(solve_long_candidates(c, s.stream, a, seg_count, launch));
   }
@@ -1050,6 +1058,32 @@ BTRAPZ_EXPORT int btrapz_solve_warm_device(btrapz_ctx *c, const btrapz_shared *s
                                         void *stream) {
   return solve_common(c, sh, opt, warm, B, seg_stride, seg_count, seg, init, ref_end, dl_bounds, ctrl, cost, status,
                       iters, stream);
+}
+
+// btrapz_solve_warm_device for candidates of up to BTRAPZ_MAX_SEGMENTS_LONG segments (include/btrapz_hip_long.h): at most
+// 64 slots per candidate -- the call is btrapz_solve_warm_device; beyond, solve_common with the long form's warm
+// instantiation for the uniform batch or, after the launch of the short candidates, for the long ones of a ragged batch.
+BTRAPZ_EXPORT int btrapz_solve_long_warm_device(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_options *opt,
+                                             const btrapz_warm *warm, int B, int seg_stride, const double *seg,
+                                             const int *seg_count, const double *init, const double *ref_end,
+                                             const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters,
+                                             void *stream) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (!options_ok(c, opt)) return BTRAPZ_EINVAL;
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: seg_stride > BTRAPZ_MAX_SEGMENTS_LONG";
+    return BTRAPZ_EINVAL;
+  }
+  if (opt && opt->elastic != 0) {
+    c->err = "invalid argument: btrapz_solve_long_warm_device has no rescue pass (btrapz_options.elastic must be 0)";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
+    return solve_common(c, sh, opt, warm, B, seg_stride, seg_count, seg, init, ref_end, dl_bounds, ctrl, cost, status, iters, stream);
+  btrapz_warm w;   // (the hint orders the packed forms' wavefronts: it says nothing to one problem per workgroup)
+  if (warm) { w = *warm; w.hint = nullptr; }
+  return solve_common(c, sh, opt, warm ? &w : nullptr, B, seg_stride, seg_count, seg, init, ref_end, dl_bounds, ctrl, cost,
+                      status, iters, stream, true);
 }
 
 // ---- entry points that take parameter sets: the sets solve, its VJP and JVP, traj_cost ---------------------------------

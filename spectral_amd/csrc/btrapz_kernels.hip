@@ -71,7 +71,10 @@ namespace btrapz {
 // back: two barriers per shifted value) and the reductions (reduce4).  Every lane of the workgroup follows the problem's
 // termination decisions (lanes beyond S compute garbage nobody reads and write nothing), so all wavefronts leave the
 // loop together.  Correctness over speed: the reference has no limit on the segment count (std::vector,
-// solve_3d.cc:323-486), its bundled inputs have at most 14.
+// solve_3d.cc:323-486), its bundled inputs have at most 14.  WARM && MULTI (btrapz_solve_long_warm_device): the same
+// workgroup mapping with the warm set-up, the cold restart and the multipliers written back; whether a start is warm
+// depends on kernel arguments only, so every wavefront reaches the barriers of the set-up's neighbour exchange, and the
+// restart is one decision per workgroup (see there).  A lane reads and writes x0, lam0 and lam_out at segment 64 wv + l.
 // CAPPED / RESUME (uniform cold batches much larger than the machine; btrapz_options.cap_iter): two launches instead of
 // one.  A wavefront runs as long as its slowest group, and a launch as long as its last wavefront: on the scenario_1
 // batch the same candidates sorted by iteration count (hard ones first) take 5.67 ms instead of 7.02.  The order cannot
@@ -96,7 +99,7 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
                                                const int *set_index = nullptr) {
   static_assert(!QUEUE || (!WARM && !ORDERED && !ELASTIC), "the queue serves uniform cold batches");
   static_assert(!SPLIT || (!ORDERED && !ELASTIC && !QUEUE), "the split form serves uniform batches");
-  static_assert(!MULTI || (!WARM && !ORDERED && !QUEUE && !SPLIT), "the long form serves uniform cold batches (and their rescue pass) -- and, launched once per segment count with a candidate list in a.order of a.bucket_S entries, the long candidates of a ragged batch");
+  static_assert(!MULTI || (!ORDERED && !QUEUE && !SPLIT && !(WARM && (ELASTIC || SETS))), "the long form serves uniform batches, cold (and their rescue pass) or warm-started -- and, launched once per segment count with a candidate list in a.order of a.bucket_S entries, the long candidates of a ragged batch");
   static_assert(!(CAPPED || RESUME) || (!WARM && !ELASTIC && !QUEUE && !SPLIT && !MULTI && !(CAPPED && RESUME)), "capped / resume: packed cold form");
   static_assert(!RESUME || ORDERED, "the resume pass reads its problems from per-axis lists");
   static_assert(!SETS || (!ELASTIC && !QUEUE && !CAPPED && !RESUME && (ORDERED ? !SPLIT && !MULTI : SPLIT || MULTI)),
@@ -123,7 +126,7 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
     }
     return r;
   };
-  constexpr bool CACHE_RP = !ELASTIC;   // see the main loop
+  constexpr bool CACHE_RP = !ELASTIC && !(WARM && MULTI);   // see the main loop
   constexpr bool FULL = ELASTIC;                 // rows kept: see rows_kept()
   constexpr int NR = rows_kept<FULL>();
   constexpr int L_LL = 0, L_LU = NR, L_ISL = 2 * NR, L_ISU = 3 * NR, L_RED = SPLIT ? 17 : 4 * NR;
@@ -722,7 +725,8 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
     // ---- 1. control points of this segment, rows, residuals, gradient ----
     // Row residuals r_l = G c - s_l - l, r_u = G c + s_u - u: constant within an iteration and needed by six row
     // loops.  Cached (36 doubles; the allocator parks them in AGPRs) they save ~100 instructions per row loop:
-    // 6.29 -> 6.04 ms.  The warm-start instantiations carry more state and would spill, so they recompute.
+    // 6.29 -> 6.04 ms.  The warm-started long form carries more state (the restart's bookkeeping, the cold start's
+    // inputs) and spills 116 B per lane with them, none without: it recomputes (CACHE_RP above).
     double c[6], gc[6], rpl_[(CACHE_RP && !SPLIT) ? NR : 1], rpu_[(CACHE_RP && !SPLIT) ? NR : 1];
     [[maybe_unused]] double rpl5[5], rpu5[5], isl5[5], isu5[5];   // split form: residuals and reciprocal slacks of the own rows
     double mu_part = 0.0, rp_part = 0.0, dscale = 0.0;
@@ -887,6 +891,12 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
     if (WARM && __any(restart_now)) {
       // wave-uniform branch; the other groups of the wavefront only lose this iteration's Newton step.  A group
       // restarts as a whole (the score is group-uniform), so the DPP reads inside cold_start stay in the group.
+      // Long form: cold_start's neighbour exchange holds workgroup barriers, so the decision must be ONE for the whole
+      // workgroup, lanes beyond S included.  It is: restart_now is a function of done, restarted, eit, it0, best_it,
+      // res_it, best_score, best_res, tiny_steps, plain, score, res and mu -- each either set from kernel arguments and
+      // the workgroup's candidate alone (begin_candidate's reduce4 over all S lanes) or updated, in every lane alike, from
+      // the reduce4 results rr (score, res, mu) and ra (the step length behind tiny_steps) and from those counters.  So all
+      // wavefronts take this branch, the `++eit` and the `continue` together, as they take `break` above together.
       if (restart_now) {
         cold_start();
         best_score = 1e300; best_it = eit + 1; it0 = eit + 1; restarted = true; best_res = 3e38f; res_it = eit + 1; tiny_steps = 0;
@@ -1373,6 +1383,14 @@ __global__ __launch_bounds__(256) void ipm_solve_long_kernel(const KernelArgs a,
   __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
   const int wv = (int)threadIdx.x >> 6;
   ipm_solve_body<false, false, false, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63, wgs, wv);
+}
+// ... warm-started, and with the multipliers kept (btrapz_solve_long_warm_device): the same grid, 2 n workgroups of
+// 64 ceil(S / 64) threads, over a uniform batch or the listed candidates of one segment count of a ragged one.
+__global__ __launch_bounds__(256) void ipm_solve_long_warm_kernel(const KernelArgs a, const double *__restrict__ mqm) {
+  __shared__ double lds[4][lds_rows<false>()][64];
+  __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
+  const int wv = (int)threadIdx.x >> 6;
+  ipm_solve_body<true, false, false, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63, wgs, wv);
 }
 // ... and its rescue pass (btrapz_options.elastic): the workgroups of the axis problems that stalled solve them again with
 // elastic rows, the others leave at once.  Up to three wavefronts (192 segments): the 18-row LDS columns of a fourth do

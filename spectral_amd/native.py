@@ -255,6 +255,12 @@ PROTOTYPES_CHECK = {
     "btrapz_check_rows_device": (_i, [_vp, _sh, _i, _vp, _i, _i] + _ragged + [_vp, C.POINTER(CRowCheck), _vp]),
 }
 EXPORTS_CHECK = tuple(PROTOTYPES_CHECK)
+
+# Every function of include/btrapz_hip_long.h, the same way (tests/test_long_warm_abi.py holds it to that header).
+PROTOTYPES_LONG = {
+    "btrapz_solve_long_warm_device": (_i, [_vp, _sh, _opt, C.POINTER(CWarm), _i, _i] + _ragged + _result + [_vp]),
+}
+EXPORTS_LONG = tuple(PROTOTYPES_LONG)
 MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
 
 
@@ -335,7 +341,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -514,12 +520,26 @@ class Context:
                           iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, stream=None, max_iter=0,
                           eps=0.0, hint=None, elastic=0, elastic_tol=0.0, lean=0):
         """btrapz_solve_warm_device: seg_count None = uniform batch; x0 / lam0 / lam_out optional."""
-        sh = CShared.from_shared(shared); opt = _options(max_iter, eps, elastic, elastic_tol, lean=lean)
-        warm = _warm(x0, lam0, lam_out, mu0, smin, hint)
-        self._check(lib().btrapz_solve_warm_device(self._h, C.byref(sh), C.byref(opt), C.byref(warm), B, seg_stride,
-                                                   _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
-                                                   _ptr(ctrl), _ptr(cost), _ptr(status), _ptr(iters), _stream(stream)),
-                    "btrapz_solve_warm_device")
+        self._warm_call("btrapz_solve_warm_device", B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost,
+                        status, iters, _warm(x0, lam0, lam_out, mu0, smin, hint), stream,
+                        _options(max_iter, eps, elastic, elastic_tol, lean=lean))
+
+    def solve_long_warm_device(self, B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
+                               iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, stream=None, max_iter=0,
+                               eps=0.0, hint=None, elastic=0, elastic_tol=0.0, lean=0):
+        """btrapz_solve_long_warm_device (include/btrapz_hip_long.h): solve_warm_device with seg_stride up to 256 -- the
+        candidates of 65..256 segments are warm-started and keep their multipliers too.  elastic != 0 is refused."""
+        self._warm_call("btrapz_solve_long_warm_device", B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl,
+                        cost, status, iters, _warm(x0, lam0, lam_out, mu0, smin, hint), stream,
+                        _options(max_iter, eps, elastic, elastic_tol, lean=lean))
+
+    def _warm_call(self, name, B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status, iters, warm,
+                   stream, opt):
+        """The two entry points that take (shared, options, btrapz_warm, a batch record, the result arrays)."""
+        sh = CShared.from_shared(shared)
+        self._check(getattr(lib(), name)(self._h, C.byref(sh), C.byref(opt), C.byref(warm), B, seg_stride, _ptr(seg),
+                                         _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds), _ptr(ctrl), _ptr(cost),
+                                         _ptr(status), _ptr(iters), _stream(stream)), name)
 
     def solve_sets_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
                           iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, hint=None, stream=None,

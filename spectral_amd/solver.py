@@ -145,13 +145,26 @@ class BatchSolver:
                                   elastic=elastic, elastic_tol=elastic_tol, queue=queue, split=split, start=start,
                                   cap_iter=cap_iter, lean=lean, compact=compact)
             return o
+        return self._warm_solve(self.ctx.solve_warm_device, r, shared, warm, keep_multipliers, out, max_iter=max_iter, eps=eps,
+                                elastic=elastic, elastic_tol=elastic_tol, lean=lean)
+
+    def _warm_solve(self, entry, r, shared, warm, keep_multipliers, out, **options):
+        """solve() with a warm start or kept multipliers, through `entry` (Context.solve_warm_device or its long sibling)."""
         w, o = self._warm(r, warm, keep_multipliers, self._out_of(r, out))
         if w["hint"] is not None:
             _check_index(w["hint"], r.B)
-        self.ctx.solve_warm_device(r.B, r.S, shared, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, o["ctrl"],
-                                   o["cost"], o["status"], o["iters"], stream=self._stream(), max_iter=max_iter, eps=eps,
-                                   elastic=elastic, elastic_tol=elastic_tol, lean=lean, **w)
+        entry(r.B, r.S, shared, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, o["ctrl"], o["cost"], o["status"],
+              o["iters"], stream=self._stream(), **options, **w)
         return o
+
+    def solve_long(self, dbatch_or_rec, shared, warm=None, keep_multipliers=False, max_iter=0, eps=0.0, out=None):
+        """solve(..., warm=, keep_multipliers=) for candidates of up to 256 segments (btrapz_solve_long_warm_device):
+        a uniform batch, or a ragged record whose stride may exceed 64.  Candidates of 65..256 segments are warm-started
+        from warm["x0"] / warm["lam"] and return their multipliers as "lam" like the shorter ones (up to 64 slots per
+        candidate the call is solve()'s own, bit for bit).  warm None and keep_multipliers False: the cold start.  No
+        rescue pass; warm["hint"] is not read beyond 64 slots.  Returns the dict solve() returns."""
+        return self._warm_solve(self.ctx.solve_long_warm_device, self._record(dbatch_or_rec), shared, warm, keep_multipliers, out,
+                                max_iter=max_iter, eps=eps)
 
     def prepare(self, dbatch, shared, out=None, **options):
         """solve(dbatch, shared, **options) prepared once: returns (call, out) where call() launches the solve on the
