@@ -19,6 +19,8 @@
 #include "../../include/btrapz_hip_schedule.h"
 #include "../../include/btrapz_hip_check.h"
 #include "../../include/btrapz_hip_long.h"
+#include "../../include/btrapz_hip_long_grad.h"
+#include "btrapz_long_grad.h"
 #include "prism_core.h"
 
 using namespace btrapz;
@@ -212,6 +214,7 @@ struct btrapz_ctx {
   bool sets_copy_pending[2] = {false, false}; int sets_stage_next = 0;
   Buf<int> d_sets_meta{bufs};       // bucket tables of a sets batch: [n_keys + 1] x 2 + [n_keys]
   Buf<double> d_mqm_unit{bufs};     // the M'QM table with every weight 1 ([2][4][21]): the solve's VJP and JVP
+  Buf<double> d_long_cost{bufs};    // btrapz_solve_long_jvp_device: the axes' shares of cost_dot, [2][T][B]
 };
 
 #define HIPCHK_AS(ctx, what, call)                                                            \
@@ -1352,6 +1355,110 @@ BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *se
   const unsigned blocks = (unsigned)(((size_t)B + gpw - 1) / gpw);
   hipLaunchKernelGGL(jvp_kernel, dim3(blocks), dim3(128), 0, stream, a);
   HIPCHK(c, hipGetLastError());
+  return ws_close(c, stream);
+}
+
+// Gradients of a solve of 65..256 segments (btrapz_solve_long_vjp_device, include/btrapz_hip_long_grad.h): one launch of
+// long_vjp_kernel (btrapz_long_grad.hip), one axis problem per workgroup of ceil(seg_stride / 64) wavefronts.  Up to 64
+// slots per candidate the call IS btrapz_solve_vjp_device.
+BTRAPZ_EXPORT int btrapz_solve_long_vjp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                            int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                            const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                            const int *status, const double *ctrl_bar, const double *cost_bar,
+                                            const btrapz_grads *out, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
+    return btrapz_solve_vjp_device(c, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                                   ctrl_bar, cost_bar, out, stream_);
+  if (!sets_in_range(sets, n_sets) || B < 1 || !seg || !ref_end || !dl_bounds || !out) {
+    c->err = "invalid argument (long vjp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays and out non-null)";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: long vjp of candidates of at most BTRAPZ_MAX_SEGMENTS_LONG segments";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl || !lam || !status) {
+    c->err = "invalid argument: long vjp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl_bar && !cost_bar) {
+    c->err = "invalid argument: long vjp needs ctrl_bar or cost_bar (both NULL)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
+  hipStream_t stream = (hipStream_t)stream_;
+  TRY(ws_open(c, stream));
+  TRY(sets_tables(c, sets, n_sets, stream));
+  TRY(unit_mqm_table(c, stream));
+  VjpArgs a;
+  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.seg_count = seg_count;
+  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
+  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
+  a.ctrl_bar = ctrl_bar; a.cost_bar = cost_bar;
+  a.g_seg = out->seg; a.g_init = out->init; a.g_ref_end = out->ref_end; a.g_dl = out->dl_bounds; a.g_shared = out->shared;
+  hipLaunchKernelGGL(long_vjp_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((seg_stride + 63) / 64)), 0, stream, a);
+  HIPCHK(c, hipGetLastError());
+  return ws_close(c, stream);
+}
+
+// Directional derivatives of a solve of 65..256 segments (btrapz_solve_long_jvp_device): one launch of long_jvp_kernel, the
+// backward kernel's mapping, and -- when cost_dot is wanted -- long_cost_dot_kernel behind it on the same stream, which
+// adds the two axes' shares (the context's [2][T][B] workspace) in the order s + l.
+BTRAPZ_EXPORT int btrapz_solve_long_jvp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                            int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                            const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                            const int *status, int T, const btrapz_tangents *tan, double *ctrl_dot,
+                                            double *cost_dot, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
+    return btrapz_solve_jvp_device(c, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                                   T, tan, ctrl_dot, cost_dot, stream_);
+  if (!sets_in_range(sets, n_sets) || B < 1 || !seg || !ref_end || !dl_bounds) {
+    c->err = "invalid argument (long jvp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays non-null)";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: long jvp of candidates of at most BTRAPZ_MAX_SEGMENTS_LONG segments";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl || !lam || !status) {
+    c->err = "invalid argument: long jvp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
+    return BTRAPZ_EINVAL;
+  }
+  if (!ctrl_dot && !cost_dot) {
+    c->err = "invalid argument: long jvp needs ctrl_dot or cost_dot (both NULL)";
+    return BTRAPZ_EINVAL;
+  }
+  if (!tan || (!tan->seg && !tan->init && !tan->ref_end && !tan->dl_bounds && !tan->shared)) {
+    c->err = "invalid argument: long jvp needs at least one tangent (all NULL)";
+    return BTRAPZ_EINVAL;
+  }
+  if (T < 1 || T > BTRAPZ_MAX_TANGENTS) {
+    c->err = "invalid argument: long jvp of 1 <= T <= BTRAPZ_MAX_TANGENTS tangents per call";
+    return BTRAPZ_EINVAL;
+  }
+  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
+  hipStream_t stream = (hipStream_t)stream_;
+  TRY(ws_open(c, stream));
+  TRY(sets_tables(c, sets, n_sets, stream));
+  TRY(unit_mqm_table(c, stream));
+  const size_t n_cost = (size_t)T * (size_t)B;
+  if (cost_dot) GROW(c, d_long_cost, sizeof(double) * 2 * n_cost);
+  JvpArgs a;
+  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.T = T; a.seg_count = seg_count;
+  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
+  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
+  a.seg_dot = tan->seg; a.init_dot = tan->init; a.ref_end_dot = tan->ref_end; a.dl_dot = tan->dl_bounds; a.shared_dot = tan->shared;
+  a.ctrl_dot = ctrl_dot; a.cost_dot = cost_dot;
+  double *cost_ws = cost_dot ? c->d_long_cost.ptr() : nullptr;
+  hipLaunchKernelGGL(long_jvp_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((seg_stride + 63) / 64)), 0, stream, a, cost_ws);
+  HIPCHK(c, hipGetLastError());
+  if (cost_dot) {
+    hipLaunchKernelGGL(long_cost_dot_kernel, dim3((unsigned)((n_cost + 255) / 256)), dim3(256), 0, stream, (const double *)cost_ws, cost_dot,
+                       (unsigned)n_cost);
+    HIPCHK(c, hipGetLastError());
+  }
   return ws_close(c, stream);
 }
 

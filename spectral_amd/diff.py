@@ -99,6 +99,42 @@ def solve(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, set_
     return _Solve.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, set_index, variant, delta)
 
 
+def _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta):
+    """_solve_kept through BatchSolver.solve_long: candidates of up to 256 segments, one parameter row (no sets)."""
+    rec = DeviceBatch.from_tensors(*_on(solver, seg, init, ref_end, dl_bounds), seg_count=seg_count)
+    sets = _sets_of_params(params, variant, delta)
+    o = solver.new_result(rec.B, rec.S, zero_ctrl=True)
+    return rec, sets, solver.solve_long(rec, sets[0], keep_multipliers=True, out=o)
+
+
+class _SolveLong(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, seg, init, ref_end, dl_bounds, params, solver, seg_count, variant, delta):
+        ctx.rec, ctx.sets, o = _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta)
+        ctx.solver, ctx.out = solver, o
+        ctx.params_shape, ctx.params_device = params.shape, params.device
+        ctx.mark_non_differentiable(o["status"])
+        return o["ctrl"], o["cost"], o["status"]
+
+    @staticmethod
+    def backward(ctx, ctrl_bar, cost_bar, _status_bar):
+        if ctrl_bar is None and cost_bar is None:
+            return (None,) * 9
+        g = ctx.solver.solve_long_vjp(ctx.rec, ctx.sets, ctx.out, ctrl_bar, cost_bar)
+        need = ctx.needs_input_grad
+        gp = _sum_rows(g["shared"], None, 1).reshape(ctx.params_shape).to(ctx.params_device) if need[4] else None
+        return (g["seg"] if need[0] else None, g["init"] if need[1] else None, g["ref_end"] if need[2] else None,
+                g["dl_bounds"] if need[3] else None, gp, None, None, None, None)
+
+
+def solve_long(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, variant=0, delta=0.1):
+    """diff.solve for candidates of up to 256 segments: the forward is BatchSolver.solve_long with the multipliers kept
+    (btrapz_solve_long_warm_device, cold start, no rescue pass), the backward one btrapz_solve_long_vjp_device launch.
+    Arguments and results as diff.solve, with S up to 256 and params ONE row [20]: solve_long has no parameter sets."""
+    _check_params(params, None)
+    return _SolveLong.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, variant, delta)
+
+
 class _TrajCost(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctrl, init, params, s_ref, l_ref, seg, solver, seg_count, set_index, status, variant, delta):
@@ -268,6 +304,34 @@ def solve_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, *, se
     for t, c in enumerate(columns):
         tan[t, :, c] = per_cand[:, c] if log else 1.0
     j = solver.solve_jvp(rec, sets, out, {"shared": tan}, set_index=set_index)
+    return dict(ctrl=out["ctrl"], cost=out["cost"], status=out["status"], dctrl=j["ctrl"], dcost=j["cost"], out=out)
+
+
+def solve_long_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, *, seg_count=None, variant=0, delta=0.1,
+                        log=False, out=None):
+    """diff.solve_jacobian for candidates of up to 256 segments: one BatchSolver.solve_long with the multipliers kept and
+    ONE btrapz_solve_long_jvp_device call with T = len(columns) unit tangents on the named columns of the parameter row.
+    params: one row [20].  Arguments, `out` (with its precondition) and the returned dict as diff.solve_jacobian."""
+    _check_params(params, None)
+    if out is not None:
+        B_, S_ = seg.shape[1], seg.shape[2]
+        if out.get("lam") is None or tuple(out["ctrl"].shape) != (B_, 12 * S_) or tuple(out["lam"].shape) != (2, 36, B_, S_) \
+                or tuple(out["status"].shape) != (B_,):
+            raise ValueError("out: the result dict of solve_long with the multipliers kept for this batch (ctrl [B, 12 S], lam [2, 36, B, S], status [B])")
+    columns = [int(c) for c in columns]
+    if not columns or min(columns) < 0 or max(columns) >= N_PARAMS:
+        raise ValueError("columns: at least one, each in [0, %d)" % N_PARAMS)
+    d = solver.device
+    if out is None:
+        rec, sets, out = _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta)
+    else:
+        rec = DeviceBatch.from_tensors(*_on(solver, seg, init, ref_end, dl_bounds), seg_count=seg_count)
+        sets = _sets_of_params(params, variant, delta)
+    row = params.detach().to(d, torch.float64).reshape(N_PARAMS)
+    tan = torch.zeros((len(columns), rec.B, N_PARAMS), dtype=torch.float64, device=d)
+    for t, c in enumerate(columns):
+        tan[t, :, c] = row[c] if log else 1.0
+    j = solver.solve_long_jvp(rec, sets, out, {"shared": tan})
     return dict(ctrl=out["ctrl"], cost=out["cost"], status=out["status"], dctrl=j["ctrl"], dcost=j["cost"], out=out)
 
 

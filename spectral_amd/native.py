@@ -261,6 +261,14 @@ PROTOTYPES_LONG = {
     "btrapz_solve_long_warm_device": (_i, [_vp, _sh, _opt, C.POINTER(CWarm), _i, _i] + _ragged + _result + [_vp]),
 }
 EXPORTS_LONG = tuple(PROTOTYPES_LONG)
+
+# Every function of include/btrapz_hip_long_grad.h, the same way (tests/test_long_grad_abi.py holds it to that header).
+PROTOTYPES_LONG_GRAD = {
+    "btrapz_solve_long_vjp_device": (_i, [_vp, _sh, _i, _vp, _i, _i] + _ragged + [_vp, _vp, _vp, _vp, _vp, C.POINTER(CGrads), _vp]),
+    "btrapz_solve_long_jvp_device": (_i, [_vp, _sh, _i, _vp, _i, _i] + _ragged + [_vp, _vp, _vp, _i, C.POINTER(CTangents), _vp, _vp,
+                                          _vp]),
+}
+EXPORTS_LONG_GRAD = tuple(PROTOTYPES_LONG_GRAD)
 MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
 
 
@@ -341,7 +349,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_GRAD.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -561,11 +569,25 @@ class Context:
         """btrapz_solve_vjp_device: gradients of a solve (elastic = 0, multipliers kept) w.r.t. its inputs.  sets = list of
         layout.Shared; set_index None = every candidate with sets[0]; seg_count None = uniform batch; ctrl_bar / cost_bar
         may be None (zero); the g_* device tensors are overwritten (None: not wanted)."""
-        grads = CGrads(_ptr(g_seg), _ptr(g_init), _ptr(g_ref_end), _ptr(g_dl_bounds), _ptr(g_shared))
-        self._check(lib().btrapz_solve_vjp_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), B, seg_stride,
-                                                  _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
-                                                  _ptr(ctrl), _ptr(lam), _ptr(status), _ptr(ctrl_bar), _ptr(cost_bar),
-                                                  C.byref(grads), _stream(stream)), "btrapz_solve_vjp_device")
+        self._vjp_call("btrapz_solve_vjp_device", B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam,
+                       status, ctrl_bar, cost_bar, CGrads(_ptr(g_seg), _ptr(g_init), _ptr(g_ref_end), _ptr(g_dl_bounds), _ptr(g_shared)),
+                       stream)
+
+    def solve_long_vjp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                              ctrl_bar, cost_bar, g_seg=None, g_init=None, g_ref_end=None, g_dl_bounds=None, g_shared=None,
+                              stream=None):
+        """btrapz_solve_long_vjp_device (include/btrapz_hip_long_grad.h): solve_vjp_device with seg_stride up to 256 -- ctrl,
+        lam and status are those of solve_long_warm_device."""
+        self._vjp_call("btrapz_solve_long_vjp_device", B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl,
+                       lam, status, ctrl_bar, cost_bar,
+                       CGrads(_ptr(g_seg), _ptr(g_init), _ptr(g_ref_end), _ptr(g_dl_bounds), _ptr(g_shared)), stream)
+
+    def _vjp_call(self, name, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status, ctrl_bar,
+                  cost_bar, grads, stream):
+        """The two entry points that take (sets, a batch record, a solve's ctrl / lam / status, cotangents, btrapz_grads)."""
+        self._check(getattr(lib(), name)(self._h, _sets_array(sets), len(sets), _ptr(set_index), B, seg_stride, _ptr(seg),
+                                         _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds), _ptr(ctrl), _ptr(lam),
+                                         _ptr(status), _ptr(ctrl_bar), _ptr(cost_bar), C.byref(grads), _stream(stream)), name)
 
     def solve_jvp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
                          T, seg_dot=None, init_dot=None, ref_end_dot=None, dl_bounds_dot=None, shared_dot=None,
@@ -573,11 +595,27 @@ class Context:
         """btrapz_solve_jvp_device: directional derivatives of a solve (elastic = 0, multipliers kept) along T tangents per
         candidate.  sets / set_index / seg_count as in solve_vjp_device; the *_dot device tensors carry a leading axis T
         (None: zero); ctrl_dot [T, B, 12 seg_stride] / cost_dot [T, B] are overwritten (either may be None)."""
-        tan = CTangents(_ptr(seg_dot), _ptr(init_dot), _ptr(ref_end_dot), _ptr(dl_bounds_dot), _ptr(shared_dot))
-        self._check(lib().btrapz_solve_jvp_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), B, seg_stride,
-                                                  _ptr(seg), _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds),
-                                                  _ptr(ctrl), _ptr(lam), _ptr(status), int(T), C.byref(tan), _ptr(ctrl_dot),
-                                                  _ptr(cost_dot), _stream(stream)), "btrapz_solve_jvp_device")
+        self._jvp_call("btrapz_solve_jvp_device", B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam,
+                       status, T, CTangents(_ptr(seg_dot), _ptr(init_dot), _ptr(ref_end_dot), _ptr(dl_bounds_dot), _ptr(shared_dot)),
+                       ctrl_dot, cost_dot, stream)
+
+    def solve_long_jvp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                              T, seg_dot=None, init_dot=None, ref_end_dot=None, dl_bounds_dot=None, shared_dot=None,
+                              ctrl_dot=None, cost_dot=None, stream=None):
+        """btrapz_solve_long_jvp_device (include/btrapz_hip_long_grad.h): solve_jvp_device with seg_stride up to 256 -- ctrl,
+        lam and status are those of solve_long_warm_device."""
+        self._jvp_call("btrapz_solve_long_jvp_device", B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl,
+                       lam, status, T,
+                       CTangents(_ptr(seg_dot), _ptr(init_dot), _ptr(ref_end_dot), _ptr(dl_bounds_dot), _ptr(shared_dot)),
+                       ctrl_dot, cost_dot, stream)
+
+    def _jvp_call(self, name, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status, T, tan,
+                  ctrl_dot, cost_dot, stream):
+        """The two entry points that take (sets, a batch record, a solve's ctrl / lam / status, T, btrapz_tangents, outputs)."""
+        self._check(getattr(lib(), name)(self._h, _sets_array(sets), len(sets), _ptr(set_index), B, seg_stride, _ptr(seg),
+                                         _ptr(seg_count), _ptr(init), _ptr(ref_end), _ptr(dl_bounds), _ptr(ctrl), _ptr(lam),
+                                         _ptr(status), int(T), C.byref(tan), _ptr(ctrl_dot), _ptr(cost_dot), _stream(stream)),
+                    name)
 
     def check_rows_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, unit=0,
                           margin=None, worst=None, eq_res=None, obj=None, stream=None):

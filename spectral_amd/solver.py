@@ -365,6 +365,20 @@ class BatchSolver:
             raise ValueError("%s needs the solve's multipliers: solve with keep_multipliers=True" % what)
         return _sets_of(shared_or_sets)
 
+    def solve_long_vjp(self, dbatch_or_rec, shared_or_sets, out, ctrl_bar, cost_bar, set_index=None):
+        """solve_vjp for candidates of up to 256 segments (btrapz_solve_long_vjp_device): `out` is the result dict of
+        solve_long(..., keep_multipliers=True).  Arguments, shapes, checks and the returned dict are solve_vjp's; up to 64
+        slots per candidate the call is solve_vjp's own, bit for bit."""
+        return self._solve_vjp(self.ctx.solve_long_vjp_device, "solve_long_vjp", dbatch_or_rec, shared_or_sets, out, ctrl_bar,
+                               cost_bar, set_index)
+
+    def solve_long_jvp(self, dbatch_or_rec, shared_or_sets, out, tangents, set_index=None):
+        """solve_jvp for candidates of up to 256 segments (btrapz_solve_long_jvp_device): `out` is the result dict of
+        solve_long(..., keep_multipliers=True).  Arguments, shapes, checks and the returned dict are solve_jvp's; up to 64
+        slots per candidate the call is solve_jvp's own, bit for bit."""
+        return self._solve_jvp(self.ctx.solve_long_jvp_device, "solve_long_jvp", dbatch_or_rec, shared_or_sets, out, tangents,
+                               set_index)
+
     def solve_vjp(self, dbatch_or_rec, shared_or_sets, out, ctrl_bar, cost_bar, set_index=None):
         """Gradients of a solve (btrapz_solve_vjp_device).  dbatch_or_rec: the DeviceBatch or ragged record that was solved;
         shared_or_sets: its layout.Shared, or the list of sets with set_index (int32 device tensor [B]); out: the solve's
@@ -372,19 +386,23 @@ class BatchSolver:
         [B, 12 S] / cost_bar [B]: cotangents (either may be None).  Returns a dict of device tensors: "seg"
         [NUM_SEG_FIELDS, B, S] (field 0 is 0), "init" [B, 6], "ref_end" [B, 2], "dl_bounds" [B, 10], "shared" [B, 20] per
         candidate (layout.Shared.as_array order, without delta)."""
+        return self._solve_vjp(self.ctx.solve_vjp_device, "solve_vjp", dbatch_or_rec, shared_or_sets, out, ctrl_bar, cost_bar,
+                               set_index)
+
+    def _solve_vjp(self, entry, what, dbatch_or_rec, shared_or_sets, out, ctrl_bar, cost_bar, set_index):
+        """solve_vjp through `entry` (Context.solve_vjp_device or its long sibling)."""
         r = self._record(dbatch_or_rec)
         B, S = r.B, r.S
-        sets = self._derivative_args("solve_vjp", r, shared_or_sets, out, set_index)
+        sets = self._derivative_args(what, r, shared_or_sets, out, set_index)
         chk = lambda t, shape: None if t is None else (t if (t.dtype == torch.float64 and t.is_contiguous() and
                                                             tuple(t.shape) == shape) else
                                                        t.to(self.device, dtype=torch.float64).reshape(shape).contiguous())
         ctrl_bar = chk(ctrl_bar, (B, 12 * S)); cost_bar = chk(cost_bar, (B,))
         g = dict(seg=self._empty(L.NUM_SEG_FIELDS, B, S), init=self._empty(B, 6), ref_end=self._empty(B, 2),
                  dl_bounds=self._empty(B, 10), shared=self._empty(B, 20))
-        self.ctx.solve_vjp_device(B, S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, out["ctrl"],
-                                  out["lam"], out["status"], ctrl_bar, cost_bar, g_seg=g["seg"], g_init=g["init"],
-                                  g_ref_end=g["ref_end"], g_dl_bounds=g["dl_bounds"], g_shared=g["shared"],
-                                  stream=self._stream())
+        entry(B, S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, out["ctrl"], out["lam"], out["status"],
+              ctrl_bar, cost_bar, g_seg=g["seg"], g_init=g["init"], g_ref_end=g["ref_end"], g_dl_bounds=g["dl_bounds"],
+              g_shared=g["shared"], stream=self._stream())
         return g
 
     def solve_jvp(self, dbatch_or_rec, shared_or_sets, out, tangents, set_index=None):
@@ -393,9 +411,13 @@ class BatchSolver:
         with any of "seg" [T, NUM_SEG_FIELDS, B, S] (field 0 is ignored), "init" [T, B, 6], "ref_end" [T, B, 2],
         "dl_bounds" [T, B, 10], "shared" [T, B, 20] (per candidate, layout.Shared.as_array order without delta); a missing
         one is zero.  Returns {"ctrl": [T, B, 12 S], "cost": [T, B]}, device tensors."""
+        return self._solve_jvp(self.ctx.solve_jvp_device, "solve_jvp", dbatch_or_rec, shared_or_sets, out, tangents, set_index)
+
+    def _solve_jvp(self, entry, what, dbatch_or_rec, shared_or_sets, out, tangents, set_index):
+        """solve_jvp through `entry` (Context.solve_jvp_device or its long sibling)."""
         r = self._record(dbatch_or_rec)
         B, S = r.B, r.S
-        sets = self._derivative_args("solve_jvp", r, shared_or_sets, out, set_index)
+        sets = self._derivative_args(what, r, shared_or_sets, out, set_index)
         unknown = set(tangents) - {"seg", "init", "ref_end", "dl_bounds", "shared"}
         if unknown:
             raise ValueError("unknown tangents: %s" % sorted(unknown))
@@ -408,10 +430,9 @@ class BatchSolver:
                 raise ValueError("tangent %r: shape %s, expected %s" % (k, tuple(v.shape), shapes[k]))
             tan[k] = self._f64(v)
         o = dict(ctrl=self._empty(max(T, 0), B, 12 * S), cost=self._empty(max(T, 0), B))
-        self.ctx.solve_jvp_device(B, S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, out["ctrl"],
-                                  out["lam"], out["status"], T, seg_dot=tan.get("seg"), init_dot=tan.get("init"),
-                                  ref_end_dot=tan.get("ref_end"), dl_bounds_dot=tan.get("dl_bounds"),
-                                  shared_dot=tan.get("shared"), ctrl_dot=o["ctrl"], cost_dot=o["cost"], stream=self._stream())
+        entry(B, S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, out["ctrl"], out["lam"], out["status"], T,
+              seg_dot=tan.get("seg"), init_dot=tan.get("init"), ref_end_dot=tan.get("ref_end"), dl_bounds_dot=tan.get("dl_bounds"),
+              shared_dot=tan.get("shared"), ctrl_dot=o["ctrl"], cost_dot=o["cost"], stream=self._stream())
         return o
 
     # ---- scores, samples, states and their derivatives ----------------------------------------
