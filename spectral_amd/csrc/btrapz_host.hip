@@ -1264,193 +1264,105 @@ BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *s
   return finalize_and_close(c, stream, B, cost, status, iters);
 }
 
-// Gradients of a solve (btrapz_solve_vjp_device): one launch of vjp_kernel (btrapz_vjp.hip), groups of S lanes as the
+// ---- gradients of a solve: btrapz_solve_vjp_device, btrapz_solve_jvp_device and their forms for 65..256 segments ----
+// The refusals the four entry points share, in their order.  what: "vjp", "long jvp", ...; out_ok: the call's own output
+// argument is there (backward: out); have_output: ctrl_bar or cost_bar, forward ctrl_dot or cost_dot; fwd: forward mode,
+// whose tangents and T are checked too.
+struct GradCall {
+  const char *what;
+  int max_segments;            // BTRAPZ_MAX_SEGMENTS or BTRAPZ_MAX_SEGMENTS_LONG
+  bool fwd, out_ok, have_output;
+  int T;
+  const btrapz_tangents *tan;
+};
+static bool grad_args_ok(btrapz_ctx *c, const GradCall &g, const btrapz_shared *sets, int n_sets, int B, int seg_stride, const double *seg,
+                         const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam, const int *status) {
+  const std::string what = g.what;
+  const bool packed = g.max_segments == BTRAPZ_MAX_SEGMENTS;
+  if (!sets_in_range(sets, n_sets) || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds || !g.out_ok)
+    c->err = "invalid argument (" + what + ": 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays" +
+             (g.fwd ? "" : " and out") + " non-null)";
+  else if (seg_stride > g.max_segments)
+    c->err = "invalid argument: " + what + " of candidates of at most " +
+             (packed ? "BTRAPZ_MAX_SEGMENTS segments (the long form keeps no multipliers)" : "BTRAPZ_MAX_SEGMENTS_LONG segments");
+  else if (!ctrl || !lam || !status)
+    c->err = "invalid argument: " + what + " needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
+  else if (!g.have_output)
+    c->err = "invalid argument: " + what + (g.fwd ? " needs ctrl_dot or cost_dot (both NULL)" : " needs ctrl_bar or cost_bar (both NULL)");
+  else if (g.fwd && (!g.tan || (!g.tan->seg && !g.tan->init && !g.tan->ref_end && !g.tan->dl_bounds && !g.tan->shared)))
+    c->err = "invalid argument: " + what + " needs at least one tangent (all NULL)";
+  else if (g.fwd && (g.T < 1 || g.T > BTRAPZ_MAX_TANGENTS))
+    c->err = "invalid argument: " + what + " of 1 <= T <= BTRAPZ_MAX_TANGENTS tangents per call";
+  else
+    return sets_alike(c, sets, n_sets);
+  return false;
+}
+
+// Opens the launch sequence, makes the tables the kernels read and fills what VjpArgs and JvpArgs have in common.
+template <class Args>
+static int fill_grad_args(btrapz_ctx *c, hipStream_t stream, Args &a, const btrapz_shared *sets, int n_sets, const int *set_index, int B,
+                          int seg_stride, const double *seg, const int *seg_count, const double *ref_end, const double *dl_bounds,
+                          const double *ctrl, const double *lam, const int *status) {
+  TRY(ws_open(c, stream));
+  TRY(sets_tables(c, sets, n_sets, stream));
+  TRY(unit_mqm_table(c, stream));
+  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.seg_count = seg_count;
+  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
+  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
+  return BTRAPZ_OK;
+}
+
+// Backward, both forms.  Up to 64 slots per candidate: one launch of vjp_kernel (btrapz_vjp.hip), groups of S lanes as the
 // packed solve lays them out -- S = seg_stride for a ragged batch, whose lanes beyond a candidate's count stay idle.
-BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
-                                       int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
-                                       const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
-                                       const int *status, const double *ctrl_bar, const double *cost_bar,
-                                       const btrapz_grads *out, void *stream_) {
-  (void)init;   // (the initial state enters the gradient through the returned control points of segment 0)
-  if (!c) return BTRAPZ_EINVAL;
-  if (!sets_in_range(sets, n_sets) || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds || !out) {
-    c->err = "invalid argument (vjp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays and out non-null)";
-    return BTRAPZ_EINVAL;
-  }
-  if (seg_stride > BTRAPZ_MAX_SEGMENTS) {
-    c->err = "invalid argument: vjp of candidates of at most BTRAPZ_MAX_SEGMENTS segments (the long form keeps no multipliers)";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl || !lam || !status) {
-    c->err = "invalid argument: vjp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl_bar && !cost_bar) {
-    c->err = "invalid argument: vjp needs ctrl_bar or cost_bar (both NULL)";
-    return BTRAPZ_EINVAL;
-  }
-  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
+// Beyond: one launch of long_vjp_kernel (btrapz_long_grad.hip), one axis problem per workgroup of ceil(seg_stride / 64)
+// wavefronts.
+static int solve_vjp(btrapz_ctx *c, const char *what, int max_segments, const btrapz_shared *sets, int n_sets, const int *set_index, int B,
+                     int seg_stride, const double *seg, const int *seg_count, const double *ref_end, const double *dl_bounds,
+                     const double *ctrl, const double *lam, const int *status, const double *ctrl_bar, const double *cost_bar,
+                     const btrapz_grads *out, void *stream_) {
+  const GradCall g = {what, max_segments, false, out != nullptr, ctrl_bar || cost_bar, 0, nullptr};
+  if (!grad_args_ok(c, g, sets, n_sets, B, seg_stride, seg, ref_end, dl_bounds, ctrl, lam, status)) return BTRAPZ_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
-  TRY(ws_open(c, stream));
-  TRY(sets_tables(c, sets, n_sets, stream));
-  TRY(unit_mqm_table(c, stream));
   VjpArgs a;
-  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.seg_count = seg_count;
-  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
-  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
+  TRY(fill_grad_args(c, stream, a, sets, n_sets, set_index, B, seg_stride, seg, seg_count, ref_end, dl_bounds, ctrl, lam, status));
   a.ctrl_bar = ctrl_bar; a.cost_bar = cost_bar;
   a.g_seg = out->seg; a.g_init = out->init; a.g_ref_end = out->ref_end; a.g_dl = out->dl_bounds; a.g_shared = out->shared;
-  const unsigned gpw = 64u / (unsigned)seg_stride;
-  const unsigned blocks = 2u * (unsigned)(((size_t)B + gpw - 1) / gpw);
-  hipLaunchKernelGGL(vjp_kernel, dim3(blocks), dim3(64), 0, stream, a);
+  if (max_segments == BTRAPZ_MAX_SEGMENTS) {
+    const unsigned gpw = 64u / (unsigned)seg_stride;
+    const unsigned blocks = 2u * (unsigned)(((size_t)B + gpw - 1) / gpw);
+    hipLaunchKernelGGL(vjp_kernel, dim3(blocks), dim3(64), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL(long_vjp_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((seg_stride + 63) / 64)), 0, stream, a);
+  }
   HIPCHK(c, hipGetLastError());
   return ws_close(c, stream);
 }
 
-// Directional derivatives of a solve (btrapz_solve_jvp_device): one launch of jvp_kernel (btrapz_jvp.hip), vjp_kernel's
-// groups of S lanes; a workgroup is the two wavefronts (s axis, l axis) of the same candidates.
-BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
-                                       int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
-                                       const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
-                                       const int *status, int T, const btrapz_tangents *tan, double *ctrl_dot,
-                                       double *cost_dot, void *stream_) {
-  (void)init;   // (the tangent system is stated at the returned control points; init_dot is what moves them)
-  if (!c) return BTRAPZ_EINVAL;
-  if (!sets_in_range(sets, n_sets) || B < 1 || seg_stride < 1 || !seg || !ref_end || !dl_bounds) {
-    c->err = "invalid argument (jvp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays non-null)";
-    return BTRAPZ_EINVAL;
-  }
-  if (seg_stride > BTRAPZ_MAX_SEGMENTS) {
-    c->err = "invalid argument: jvp of candidates of at most BTRAPZ_MAX_SEGMENTS segments (the long form keeps no multipliers)";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl || !lam || !status) {
-    c->err = "invalid argument: jvp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl_dot && !cost_dot) {
-    c->err = "invalid argument: jvp needs ctrl_dot or cost_dot (both NULL)";
-    return BTRAPZ_EINVAL;
-  }
-  if (!tan || (!tan->seg && !tan->init && !tan->ref_end && !tan->dl_bounds && !tan->shared)) {
-    c->err = "invalid argument: jvp needs at least one tangent (all NULL)";
-    return BTRAPZ_EINVAL;
-  }
-  if (T < 1 || T > BTRAPZ_MAX_TANGENTS) {
-    c->err = "invalid argument: jvp of 1 <= T <= BTRAPZ_MAX_TANGENTS tangents per call";
-    return BTRAPZ_EINVAL;
-  }
-  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
-  hipStream_t stream = (hipStream_t)stream_;
-  TRY(ws_open(c, stream));
-  TRY(sets_tables(c, sets, n_sets, stream));
-  TRY(unit_mqm_table(c, stream));
-  JvpArgs a;
-  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.T = T; a.seg_count = seg_count;
-  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
-  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
-  a.seg_dot = tan->seg; a.init_dot = tan->init; a.ref_end_dot = tan->ref_end; a.dl_dot = tan->dl_bounds; a.shared_dot = tan->shared;
-  a.ctrl_dot = ctrl_dot; a.cost_dot = cost_dot;
-  const unsigned gpw = 64u / (unsigned)seg_stride;
-  const unsigned blocks = (unsigned)(((size_t)B + gpw - 1) / gpw);
-  hipLaunchKernelGGL(jvp_kernel, dim3(blocks), dim3(128), 0, stream, a);
-  HIPCHK(c, hipGetLastError());
-  return ws_close(c, stream);
-}
-
-// Gradients of a solve of 65..256 segments (btrapz_solve_long_vjp_device, include/btrapz_hip_long_grad.h): one launch of
-// long_vjp_kernel (btrapz_long_grad.hip), one axis problem per workgroup of ceil(seg_stride / 64) wavefronts.  Up to 64
-// slots per candidate the call IS btrapz_solve_vjp_device.
-BTRAPZ_EXPORT int btrapz_solve_long_vjp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
-                                            int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
-                                            const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
-                                            const int *status, const double *ctrl_bar, const double *cost_bar,
-                                            const btrapz_grads *out, void *stream_) {
-  if (!c) return BTRAPZ_EINVAL;
-  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
-    return btrapz_solve_vjp_device(c, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
-                                   ctrl_bar, cost_bar, out, stream_);
-  if (!sets_in_range(sets, n_sets) || B < 1 || !seg || !ref_end || !dl_bounds || !out) {
-    c->err = "invalid argument (long vjp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays and out non-null)";
-    return BTRAPZ_EINVAL;
-  }
-  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
-    c->err = "invalid argument: long vjp of candidates of at most BTRAPZ_MAX_SEGMENTS_LONG segments";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl || !lam || !status) {
-    c->err = "invalid argument: long vjp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl_bar && !cost_bar) {
-    c->err = "invalid argument: long vjp needs ctrl_bar or cost_bar (both NULL)";
-    return BTRAPZ_EINVAL;
-  }
-  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
-  hipStream_t stream = (hipStream_t)stream_;
-  TRY(ws_open(c, stream));
-  TRY(sets_tables(c, sets, n_sets, stream));
-  TRY(unit_mqm_table(c, stream));
-  VjpArgs a;
-  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.seg_count = seg_count;
-  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
-  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
-  a.ctrl_bar = ctrl_bar; a.cost_bar = cost_bar;
-  a.g_seg = out->seg; a.g_init = out->init; a.g_ref_end = out->ref_end; a.g_dl = out->dl_bounds; a.g_shared = out->shared;
-  hipLaunchKernelGGL(long_vjp_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((seg_stride + 63) / 64)), 0, stream, a);
-  HIPCHK(c, hipGetLastError());
-  return ws_close(c, stream);
-}
-
-// Directional derivatives of a solve of 65..256 segments (btrapz_solve_long_jvp_device): one launch of long_jvp_kernel, the
+// Forward mode, both forms.  Up to 64 slots: one launch of jvp_kernel (btrapz_jvp.hip), vjp_kernel's groups of S lanes; a
+// workgroup is the two wavefronts (s axis, l axis) of the same candidates.  Beyond: one launch of long_jvp_kernel, the
 // backward kernel's mapping, and -- when cost_dot is wanted -- long_cost_dot_kernel behind it on the same stream, which
 // adds the two axes' shares (the context's [2][T][B] workspace) in the order s + l.
-BTRAPZ_EXPORT int btrapz_solve_long_jvp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
-                                            int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
-                                            const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
-                                            const int *status, int T, const btrapz_tangents *tan, double *ctrl_dot,
-                                            double *cost_dot, void *stream_) {
-  if (!c) return BTRAPZ_EINVAL;
-  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
-    return btrapz_solve_jvp_device(c, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
-                                   T, tan, ctrl_dot, cost_dot, stream_);
-  if (!sets_in_range(sets, n_sets) || B < 1 || !seg || !ref_end || !dl_bounds) {
-    c->err = "invalid argument (long jvp: 1 <= n_sets <= BTRAPZ_MAX_SETS, B >= 1, seg_stride >= 1, the batch arrays non-null)";
-    return BTRAPZ_EINVAL;
-  }
-  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
-    c->err = "invalid argument: long jvp of candidates of at most BTRAPZ_MAX_SEGMENTS_LONG segments";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl || !lam || !status) {
-    c->err = "invalid argument: long jvp needs the solve's ctrl, lam (btrapz_warm.lam_out) and status";
-    return BTRAPZ_EINVAL;
-  }
-  if (!ctrl_dot && !cost_dot) {
-    c->err = "invalid argument: long jvp needs ctrl_dot or cost_dot (both NULL)";
-    return BTRAPZ_EINVAL;
-  }
-  if (!tan || (!tan->seg && !tan->init && !tan->ref_end && !tan->dl_bounds && !tan->shared)) {
-    c->err = "invalid argument: long jvp needs at least one tangent (all NULL)";
-    return BTRAPZ_EINVAL;
-  }
-  if (T < 1 || T > BTRAPZ_MAX_TANGENTS) {
-    c->err = "invalid argument: long jvp of 1 <= T <= BTRAPZ_MAX_TANGENTS tangents per call";
-    return BTRAPZ_EINVAL;
-  }
-  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
+static int solve_jvp(btrapz_ctx *c, const char *what, int max_segments, const btrapz_shared *sets, int n_sets, const int *set_index, int B,
+                     int seg_stride, const double *seg, const int *seg_count, const double *ref_end, const double *dl_bounds,
+                     const double *ctrl, const double *lam, const int *status, int T, const btrapz_tangents *tan, double *ctrl_dot,
+                     double *cost_dot, void *stream_) {
+  const GradCall g = {what, max_segments, true, true, ctrl_dot || cost_dot, T, tan};
+  if (!grad_args_ok(c, g, sets, n_sets, B, seg_stride, seg, ref_end, dl_bounds, ctrl, lam, status)) return BTRAPZ_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
-  TRY(ws_open(c, stream));
-  TRY(sets_tables(c, sets, n_sets, stream));
-  TRY(unit_mqm_table(c, stream));
-  const size_t n_cost = (size_t)T * (size_t)B;
-  if (cost_dot) GROW(c, d_long_cost, sizeof(double) * 2 * n_cost);
   JvpArgs a;
-  a.B = B; a.S = seg_stride; a.seg_stride = seg_stride; a.T = T; a.seg_count = seg_count;
-  a.sets = c->d_sets; a.n_sets = n_sets; a.set_index = set_index; a.mqm = c->d_mqm_sets; a.mqm_unit = c->d_mqm_unit;
-  a.seg = seg; a.ref_end = ref_end; a.dl_bounds = dl_bounds; a.ctrl = ctrl; a.lam = lam; a.status = status;
+  TRY(fill_grad_args(c, stream, a, sets, n_sets, set_index, B, seg_stride, seg, seg_count, ref_end, dl_bounds, ctrl, lam, status));
+  a.T = T;
   a.seg_dot = tan->seg; a.init_dot = tan->init; a.ref_end_dot = tan->ref_end; a.dl_dot = tan->dl_bounds; a.shared_dot = tan->shared;
   a.ctrl_dot = ctrl_dot; a.cost_dot = cost_dot;
+  if (max_segments == BTRAPZ_MAX_SEGMENTS) {
+    const unsigned gpw = 64u / (unsigned)seg_stride;
+    const unsigned blocks = (unsigned)(((size_t)B + gpw - 1) / gpw);
+    hipLaunchKernelGGL(jvp_kernel, dim3(blocks), dim3(128), 0, stream, a);
+    HIPCHK(c, hipGetLastError());
+    return ws_close(c, stream);
+  }
+  const size_t n_cost = (size_t)T * (size_t)B;
+  if (cost_dot) GROW(c, d_long_cost, sizeof(double) * 2 * n_cost);
   double *cost_ws = cost_dot ? c->d_long_cost.ptr() : nullptr;
   hipLaunchKernelGGL(long_jvp_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((seg_stride + 63) / 64)), 0, stream, a, cost_ws);
   HIPCHK(c, hipGetLastError());
@@ -1460,6 +1372,57 @@ BTRAPZ_EXPORT int btrapz_solve_long_jvp_device(btrapz_ctx *c, const btrapz_share
     HIPCHK(c, hipGetLastError());
   }
   return ws_close(c, stream);
+}
+
+// (init: the initial state enters the gradient through the returned control points of segment 0; forward, the tangent
+//  system is stated at the returned control points and init_dot is what moves them)
+BTRAPZ_EXPORT int btrapz_solve_vjp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                       int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                       const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                       const int *status, const double *ctrl_bar, const double *cost_bar,
+                                       const btrapz_grads *out, void *stream_) {
+  (void)init;
+  if (!c) return BTRAPZ_EINVAL;
+  return solve_vjp(c, "vjp", BTRAPZ_MAX_SEGMENTS, sets, n_sets, set_index, B, seg_stride, seg, seg_count, ref_end, dl_bounds, ctrl, lam,
+                   status, ctrl_bar, cost_bar, out, stream_);
+}
+
+BTRAPZ_EXPORT int btrapz_solve_jvp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                       int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                       const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                       const int *status, int T, const btrapz_tangents *tan, double *ctrl_dot,
+                                       double *cost_dot, void *stream_) {
+  (void)init;
+  if (!c) return BTRAPZ_EINVAL;
+  return solve_jvp(c, "jvp", BTRAPZ_MAX_SEGMENTS, sets, n_sets, set_index, B, seg_stride, seg, seg_count, ref_end, dl_bounds, ctrl, lam,
+                   status, T, tan, ctrl_dot, cost_dot, stream_);
+}
+
+// Solves of 65..256 segments (include/btrapz_hip_long_grad.h).  Up to 64 slots per candidate the calls ARE the two above.
+BTRAPZ_EXPORT int btrapz_solve_long_vjp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                            int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                            const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                            const int *status, const double *ctrl_bar, const double *cost_bar,
+                                            const btrapz_grads *out, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
+    return btrapz_solve_vjp_device(c, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                                   ctrl_bar, cost_bar, out, stream_);
+  return solve_vjp(c, "long vjp", BTRAPZ_MAX_SEGMENTS_LONG, sets, n_sets, set_index, B, seg_stride, seg, seg_count, ref_end, dl_bounds, ctrl,
+                   lam, status, ctrl_bar, cost_bar, out, stream_);
+}
+
+BTRAPZ_EXPORT int btrapz_solve_long_jvp_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                            int B, int seg_stride, const double *seg, const int *seg_count, const double *init,
+                                            const double *ref_end, const double *dl_bounds, const double *ctrl, const double *lam,
+                                            const int *status, int T, const btrapz_tangents *tan, double *ctrl_dot,
+                                            double *cost_dot, void *stream_) {
+  if (!c) return BTRAPZ_EINVAL;
+  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
+    return btrapz_solve_jvp_device(c, sets, n_sets, set_index, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
+                                   T, tan, ctrl_dot, cost_dot, stream_);
+  return solve_jvp(c, "long jvp", BTRAPZ_MAX_SEGMENTS_LONG, sets, n_sets, set_index, B, seg_stride, seg, seg_count, ref_end, dl_bounds, ctrl,
+                   lam, status, T, tan, ctrl_dot, cost_dot, stream_);
 }
 
 // The audit of given control points against every row of their QP (btrapz_check_rows_device, include/btrapz_hip_check.h):

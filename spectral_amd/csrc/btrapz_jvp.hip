@@ -15,25 +15,16 @@
 //     (Phi' (P + G' D G) Phi) dX = Phi' (-(dP x + dq) - P dx_p + G' (D d - w)),   w += D (G dx_h - d),
 // D = rho_r on active rows (the VJP's rho).  The record, the bounds, P, the active set and the penalised block-tridiagonal
 // matrix are built ONCE and factorised ONCE per axis problem; the factor (K, F: 15 doubles per lane) stays in registers
-// while the kernel loops over the T tangents: right-hand side, JVP_PASSES passes, back-substitution, store.
+// while the kernel loops over the T tangents: right-hand side, GRAD_PASSES passes, back-substitution, store.
 //
 // Mapping: vjp_kernel's -- one lane per segment, a group of S lanes per axis problem, floor(64 / S) problems per
 // wavefront, one axis per wavefront; ragged lanes beyond a candidate's count decoupled.  A workgroup is the two wavefronts
 // (s axis, l axis) of the same candidates, so that cost_dot -- the one output both axes contribute to -- is summed through
 // LDS in a fixed order (s + l) and written by one lane.  Every other entry is written by the lane that owns it: no atomics.
 #include <hip/hip_runtime.h>
-#include "btrapz_ipm.h"
+#include "btrapz_grad_rule.h"
 
 namespace btrapz {
-
-#define JVP_RHO 1e6
-#define HSYM(H, i, j) ((i) <= (j) ? H[SYM(i, j)] : H[SYM(j, i)])
-#define JVP_PASSES 3
-#define JVP_SLACK_ACTIVE 3.1622776601683794e-4   // vjp_kernel's VJP_SLACK_ACTIVE: rows whose kept multiplier is no number
-
-// rows this kernel keeps: those of the solve (rows_kept<false>: 1-5, 7-10, 12-17)
-#define JVP_ROWS(r) static_for<15>([&](auto r##_c) { constexpr int r = row_id<false>(decltype(r##_c)::value); constexpr int ri_ = state_index<false>(r); (void)ri_;
-#define JVP_END });
 
 __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
   __shared__ double red_[2][4][64];
@@ -182,16 +173,16 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
   {
     const size_t lam_row = BS;
     const size_t lam_e = (size_t)axis * 36 * lam_row + e;
-    JVP_ROWS(r)
+    GRAD_ROWS(r)
       const double gc = row_dot<r>(c, t);
       const double ll = act ? a.lam[lam_e + (size_t)r * lam_row] : 0.0, lu = act ? a.lam[lam_e + (size_t)(18 + r) * lam_row] : 0.0;
       const double lo = VLO(r), up = VUP(r);
-      const bool al = (fabs(ll) < 1e300 ? ll > gc - lo : gc - lo < JVP_SLACK_ACTIVE) && !(fabs(lo) >= BTRAPZ_FAR);
-      const bool au = (fabs(lu) < 1e300 ? lu > up - gc : up - gc < JVP_SLACK_ACTIVE) && !(fabs(up) >= BTRAPZ_FAR);
+      const bool al = (fabs(ll) < 1e300 ? ll > gc - lo : gc - lo < GRAD_SLACK_ACTIVE) && !(fabs(lo) >= BTRAPZ_FAR);
+      const bool au = (fabs(lu) < 1e300 ? lu > up - gc : up - gc < GRAD_SLACK_ACTIVE) && !(fabs(up) >= BTRAPZ_FAR);
       side[ri_] = (act && (al || au)) ? ((al && au) ? (ll >= lu ? -1 : 1) : (al ? -1 : 1)) : 0;
-      rho[ri_] = side[ri_] != 0 ? JVP_RHO * pscale / (r < 6 ? t2 : r < 11 ? 50.0 : r < 15 ? 2400.0 : 72000.0) : 0.0;
+      rho[ri_] = side[ri_] != 0 ? GRAD_RHO * pscale / (r < 6 ? t2 : r < 11 ? 50.0 : r < 15 ? 2400.0 : 72000.0) : 0.0;
       w[ri_] = 0.0;
-    JVP_END
+    GRAD_END
   }
 
   // ---- reduced matrix: T = M11_k + M00_(k+1), M01 couples X_(k-1) (rows) and X_k (cols) ----
@@ -199,9 +190,9 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
   {
     double H[21];
     UNROLL for (int i = 0; i < 21; i++) H[i] = Pk[i];
-    JVP_ROWS(r)
+    GRAD_ROWS(r)
       row_outer<r>(rho[ri_], t2, H);
-    JVP_END
+    GRAD_END
     if (!act) {   // (a lane without a segment: a decoupled identity)
       UNROLL for (int i = 0; i < 21; i++) H[i] = 0.0;
       UNROLL for (int i = 0; i < 6; i++) H[SYM(i, i)] = 1.0;
@@ -304,7 +295,7 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
       double dvl[5], dvh[5];
       UNROLL for (int i = 0; i < 5; i++) { dvl[i] = vlo_f[i] * dvlo_in[i]; dvh[i] = vhi_f[i] * dvhi_in[i]; }
       const double n_plo = dpp_next(dplo0), n_phi = dpp_next(dphi0), n_vlo = dpp_next(dvl[0]), n_vhi = dpp_next(dvh[0]);
-      JVP_ROWS(r)
+      GRAD_ROWS(r)
         double dl, du;
         if constexpr (r < 6) {
           dl = (r == 5 && nx_plo) ? n_plo : dplo0 + (double)r * dplod;
@@ -320,7 +311,7 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
         }
         d[ri_] = (side[ri_] < 0 ? dl : side[ri_] > 0 ? du : 0.0) - row_dot<r>(xp, t);
         w[ri_] = 0.0;
-      JVP_END
+      GRAD_END
     }
     // ---- dq (q = M' qp, last segment's end term) and dP x ----
     double dq[6], dPc[6];
@@ -359,12 +350,12 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
 
     // ---- passes of the method of multipliers (vjp_kernel's, with the constraint target d) ----
     double v[6];   // dx_h in control-point space (this segment)
-    for (int pass = 0; pass < JVP_PASSES; ++pass) {
+    for (int pass = 0; pass < GRAD_PASSES; ++pass) {
       double h[6];
       UNROLL for (int i = 0; i < 6; i++) h[i] = f[i];
-      JVP_ROWS(r)
+      GRAD_ROWS(r)
         row_scatter<r>(rho[ri_] * d[ri_] - w[ri_], t, h);
-      JVP_END
+      GRAD_END
       if (!act) { UNROLL for (int i = 0; i < 6; i++) h[i] = 0.0; }
       double u[3];
       {
@@ -405,9 +396,9 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
       UNROLL for (int i = 0; i < 3; i++) { const double vv = dpp_prev(X[i]); Xp[i] = first ? 0.0 : vv; }   // (dx_p carries the initial state)
       U_apply(nm, Xp, v[0], v[1], v[2]);
       V_apply(nm, X, v[3], v[4], v[5]);
-      JVP_ROWS(r)
+      GRAD_ROWS(r)
         w[ri_] += rho[ri_] * (row_dot<r>(v, t) - d[ri_]);
-      JVP_END
+      GRAD_END
     }
     // ---- dx = dx_h + dx_p, dcost = (P x + q)' dx + x' dP x / 2 + dq' x ----
     double dc = 0.0;
@@ -427,6 +418,8 @@ __global__ __launch_bounds__(128) void jvp_kernel(const JvpArgs a) {
   __syncthreads();
   if (axis == 0 && k == 0 && cand_in && a.cost_dot)
     for (int tau = 0; tau < a.T; ++tau) a.cost_dot[(size_t)tau * a.B + b] = ok ? cst[0][tau][g] + cst[1][tau][g] : 0.0;
+#undef VLO
+#undef VUP
 }
 
 }  // namespace btrapz

@@ -18,27 +18,17 @@
 //   * cost_dot: the two axes of a candidate are two workgroups, so each writes its share to a [2][T][B] workspace and
 //     long_cost_dot_kernel, launched behind on the same stream, adds s + l.  No atomics.
 //
-// Barriers: every __syncthreads() below stands in straight-line code or in a loop over W, LG_PASSES or
+// Barriers: every __syncthreads() below stands in straight-line code or in a loop over W, GRAD_PASSES or
 // a.T -- kernel arguments and constants.  ok, act and the segment count select DATA (and the trip count of the
 // barrier-free inner step loops); nothing returns before the last barrier.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "btrapz_ipm.h"
+#include "btrapz_grad_rule.h"
 #include "btrapz_long_grad.h"
 
 namespace btrapz {
-
-#define LG_RHO 1e6
-#define HSYM(H, i, j) ((i) <= (j) ? H[SYM(i, j)] : H[SYM(j, i)])
-#define LG_PASSES 3
-// vjp_kernel's VJP_SLACK_ACTIVE: a row whose kept multiplier is no number is classified by its slack alone
-#define LG_SLACK_ACTIVE 3.1622776601683794e-4
-
-// rows these kernels keep: those of the solve (rows_kept<false>: 1-5, 7-10, 12-17)
-#define LG_ROWS(r) static_for<15>([&](auto r##_c) { constexpr int r = row_id<false>(decltype(r##_c)::value); constexpr int ri_ = state_index<false>(r); (void)ri_;
-#define LG_END });
 
 enum { LG_EDGE = 9, LG_LANES = 256 };
 
@@ -324,16 +314,16 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
   {
     const size_t lam_row = BS;
     const size_t lam_e = (size_t)axis * 36 * lam_row + e;
-    LG_ROWS(r)
+    GRAD_ROWS(r)
       const double gc = row_dot<r>(c, t);
       const double ll = act ? a.lam[lam_e + (size_t)r * lam_row] : 0.0, lu = act ? a.lam[lam_e + (size_t)(18 + r) * lam_row] : 0.0;
       const double lo = VLO(r), up = VUP(r);
-      const bool al = (fabs(ll) < 1e300 ? ll > gc - lo : gc - lo < LG_SLACK_ACTIVE) && !(fabs(lo) >= BTRAPZ_FAR);
-      const bool au = (fabs(lu) < 1e300 ? lu > up - gc : up - gc < LG_SLACK_ACTIVE) && !(fabs(up) >= BTRAPZ_FAR);
+      const bool al = (fabs(ll) < 1e300 ? ll > gc - lo : gc - lo < GRAD_SLACK_ACTIVE) && !(fabs(lo) >= BTRAPZ_FAR);
+      const bool au = (fabs(lu) < 1e300 ? lu > up - gc : up - gc < GRAD_SLACK_ACTIVE) && !(fabs(up) >= BTRAPZ_FAR);
       side[ri_] = (act && (al || au)) ? ((al && au) ? (ll >= lu ? -1 : 1) : (al ? -1 : 1)) : 0;
-      rho[ri_] = side[ri_] != 0 ? LG_RHO * pscale / (r < 6 ? t2 : r < 11 ? 50.0 : r < 15 ? 2400.0 : 72000.0) : 0.0;
+      rho[ri_] = side[ri_] != 0 ? GRAD_RHO * pscale / (r < 6 ? t2 : r < 11 ? 50.0 : r < 15 ? 2400.0 : 72000.0) : 0.0;
       w[ri_] = 0.0;
-    LG_END
+    GRAD_END
   }
 
   // ---- reduced matrix: T = M11_k + M00_(k+1), M01 couples X_(k-1) (rows) and X_k (cols) ----
@@ -341,9 +331,9 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
   {
     double H[21];
     UNROLL for (int i = 0; i < 21; i++) H[i] = Pk[i];
-    LG_ROWS(r)
+    GRAD_ROWS(r)
       row_outer<r>(rho[ri_], t2, H);
-    LG_END
+    GRAD_END
     if (!act) {   // (a lane without a segment: a decoupled identity)
       UNROLL for (int i = 0; i < 21; i++) H[i] = 0.0;
       UNROLL for (int i = 0; i < 6; i++) H[SYM(i, i)] = 1.0;
@@ -393,12 +383,12 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
 
     // ---- passes of the method of multipliers ----
     double v[6];   // v in control-point space (this segment)
-    for (int pass = 0; pass < LG_PASSES; ++pass) {
+    for (int pass = 0; pass < GRAD_PASSES; ++pass) {
       double h[6];
       UNROLL for (int i = 0; i < 6; i++) h[i] = xb[i];
-      LG_ROWS(r)
+      GRAD_ROWS(r)
         row_scatter<r>(-w[ri_], t, h);
-      LG_END
+      GRAD_END
       if (!act) { UNROLL for (int i = 0; i < 6; i++) h[i] = 0.0; }
       double u[3];
       {
@@ -415,9 +405,9 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
       from_prev(g, X, Xp);   // (the initial state is given: 0 for segment 0)
       U_apply(nm, Xp, v[0], v[1], v[2]);
       V_apply(nm, X, v[3], v[4], v[5]);
-      LG_ROWS(r)
+      GRAD_ROWS(r)
         w[ri_] += rho[ri_] * row_dot<r>(v, t);
-      LG_END
+      GRAD_END
     }
     if (!act) { UNROLL for (int i = 0; i < 6; i++) v[i] = 0.0; }
 
@@ -428,7 +418,7 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
     double g_alo = 0.0, g_ahi = 0.0, g_jlo = 0.0, g_jhi = 0.0;
     double to_next[4] = {0.0, 0.0, 0.0, 0.0};   // amounts for the next segment's plo0, phi0, vlo[0], vhi[0]
     double own0[4];                             // (this segment's own row-0 / row-6 amounts come from the previous lane)
-    LG_ROWS(r)
+    GRAD_ROWS(r)
       const double wl = side[ri_] < 0 ? w[ri_] : 0.0, wu = side[ri_] > 0 ? w[ri_] : 0.0;
       if constexpr (r < 6) {
         if (r == 5 && nx_plo) to_next[0] += wl; else { g_lb += wl * lo0_b; g_ls += wl * (lo0_s + (double)r * lod_s); }
@@ -442,7 +432,7 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
       } else {
         g_jlo += wl * jlo_f; g_jhi += wu * jhi_f;
       }
-    LG_END
+    GRAD_END
     from_prev(g, to_next, own0);
     g_lb += own0[0] * lo0_b; g_ls += own0[0] * lo0_s;
     g_ub += own0[1] * hi0_b; g_us += own0[1] * hi0_s;
@@ -489,9 +479,9 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
         UNROLL for (int j = 0; j < 6; j++) s += HSYM(Pk, i, j) * v[j];
         r6[i] = xb[i] - s;
       }
-      LG_ROWS(r)
+      GRAD_ROWS(r)
         row_scatter<r>(-w[ri_], t, r6);
-      LG_END
+      GRAD_END
       UT_apply(nm, r6[0], r6[1], r6[2], g_init);
     }
 
@@ -594,7 +584,7 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
         double nb[4];
         from_next(g, own, nb);
         const double n_plo = nb[0], n_phi = nb[1], n_vlo = nb[2], n_vhi = nb[3];
-        LG_ROWS(r)
+        GRAD_ROWS(r)
           double dl, du;
           if constexpr (r < 6) {
             dl = (r == 5 && nx_plo) ? n_plo : dplo0 + (double)r * dplod;
@@ -610,7 +600,7 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
           }
           d[ri_] = (side[ri_] < 0 ? dl : side[ri_] > 0 ? du : 0.0) - row_dot<r>(xp, t);
           w[ri_] = 0.0;
-        LG_END
+        GRAD_END
       }
       // ---- dq (q = M' qp, last segment's end term) and dP x ----
       double dq[6], dPc[6];
@@ -649,12 +639,12 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
 
       // ---- passes of the method of multipliers (the backward kernel's, with the constraint target d) ----
       double v[6];   // dx_h in control-point space (this segment)
-      for (int pass = 0; pass < LG_PASSES; ++pass) {
+      for (int pass = 0; pass < GRAD_PASSES; ++pass) {
         double h[6];
         UNROLL for (int i = 0; i < 6; i++) h[i] = f[i];
-        LG_ROWS(r)
+        GRAD_ROWS(r)
           row_scatter<r>(rho[ri_] * d[ri_] - w[ri_], t, h);
-        LG_END
+        GRAD_END
         if (!act) { UNROLL for (int i = 0; i < 6; i++) h[i] = 0.0; }
         double u[3];
         {
@@ -671,9 +661,9 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
         from_prev(g, X, Xp);   // (dx_p carries the initial state: 0 for segment 0)
         U_apply(nm, Xp, v[0], v[1], v[2]);
         V_apply(nm, X, v[3], v[4], v[5]);
-        LG_ROWS(r)
+        GRAD_ROWS(r)
           w[ri_] += rho[ri_] * (row_dot<r>(v, t) - d[ri_]);
-        LG_END
+        GRAD_END
       }
       // ---- dx = dx_h + dx_p, dcost = (P x + q)' dx + x' dP x / 2 + dq' x ----
       double dc = 0.0;
@@ -690,6 +680,8 @@ template <class Args> __device__ __forceinline__ void long_grad_body(const Args 
       }
     }
   }
+#undef VLO
+#undef VUP
 }
 
 #define LG_PLACE                                                                                          \

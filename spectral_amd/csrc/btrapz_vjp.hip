@@ -11,7 +11,7 @@
 // The equalities are eliminated exactly, as the solve does: v = Phi vX, vX the joint states (btrapz_ipm.h NullMap), so
 // the system is block tridiagonal with 3x3 blocks.  The active rows enter by the method of multipliers:
 //     (Phi' (P + G' D G) Phi) vX = Phi' (xbar' - G' w),   w += D G Phi vX,
-// D = rho_r on active rows, rho_r = VJP_RHO times the lane's largest diagonal entry of P over |g_r|^2.  Every pass
+// D = rho_r on active rows, rho_r = GRAD_RHO times the lane's largest diagonal entry of P over |g_r|^2.  Every pass
 // divides the constraint error G v by about rho / |P|, while rho stays small enough (1e6) that the penalised matrix
 // loses no more than about six digits to its condition.  One factorisation serves all passes.
 //
@@ -20,23 +20,9 @@
 // segment count decoupled (the results are those of the uniform layout, bit for bit).  Reductions over a group:
 // group_reduce (fixed order).  Each axis writes its own entries of every output: no atomics.
 #include <hip/hip_runtime.h>
-#include "btrapz_ipm.h"
+#include "btrapz_grad_rule.h"
 
 namespace btrapz {
-
-#define VJP_RHO 1e6
-#define HSYM(H, i, j) ((i) <= (j) ? H[SYM(i, j)] : H[SYM(j, i)])
-#define VJP_PASSES 3
-// A multiplier that is no number classifies nothing.  The solve returns the control points of its BEST iterate and the
-// multipliers of its LAST one, and the last one may be the non-finite iterate that ended the solve (a warm start
-// sanitises such entries: btrapz_kernels.hip).  Such a row is classified by its slack alone, at the value the rule
-// "multiplier above slack" takes on a solved candidate: lam s = mu <= 1e-7 (BTRAPZ_SOLVED), so lam > s where
-// s < sqrt(1e-7).  Multipliers below 1e300 in size classify as before, bit for bit.
-#define VJP_SLACK_ACTIVE 3.1622776601683794e-4
-
-// rows this kernel keeps: those of the solve (rows_kept<false>: 1-5, 7-10, 12-17)
-#define VJP_ROWS(r) static_for<15>([&](auto r##_c) { constexpr int r = row_id<false>(decltype(r##_c)::value); constexpr int ri_ = state_index<false>(r); (void)ri_;
-#define VJP_END });
 
 __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
   __shared__ double red[4][64];
@@ -188,16 +174,16 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
   {
     const size_t lam_row = BS;
     const size_t lam_e = (size_t)axis * 36 * lam_row + e;
-    VJP_ROWS(r)
+    GRAD_ROWS(r)
       const double gc = row_dot<r>(c, t);
       const double ll = act ? a.lam[lam_e + (size_t)r * lam_row] : 0.0, lu = act ? a.lam[lam_e + (size_t)(18 + r) * lam_row] : 0.0;
       const double lo = VLO(r), up = VUP(r);
-      const bool al = (fabs(ll) < 1e300 ? ll > gc - lo : gc - lo < VJP_SLACK_ACTIVE) && !(fabs(lo) >= BTRAPZ_FAR);
-      const bool au = (fabs(lu) < 1e300 ? lu > up - gc : up - gc < VJP_SLACK_ACTIVE) && !(fabs(up) >= BTRAPZ_FAR);
+      const bool al = (fabs(ll) < 1e300 ? ll > gc - lo : gc - lo < GRAD_SLACK_ACTIVE) && !(fabs(lo) >= BTRAPZ_FAR);
+      const bool au = (fabs(lu) < 1e300 ? lu > up - gc : up - gc < GRAD_SLACK_ACTIVE) && !(fabs(up) >= BTRAPZ_FAR);
       side[ri_] = (act && (al || au)) ? ((al && au) ? (ll >= lu ? -1 : 1) : (al ? -1 : 1)) : 0;
-      rho[ri_] = side[ri_] != 0 ? VJP_RHO * pscale / (r < 6 ? t2 : r < 11 ? 50.0 : r < 15 ? 2400.0 : 72000.0) : 0.0;
+      rho[ri_] = side[ri_] != 0 ? GRAD_RHO * pscale / (r < 6 ? t2 : r < 11 ? 50.0 : r < 15 ? 2400.0 : 72000.0) : 0.0;
       w[ri_] = 0.0;
-    VJP_END
+    GRAD_END
   }
 
   // ---- reduced matrix: T = M11_k + M00_(k+1), M01 couples X_(k-1) (rows) and X_k (cols) ----
@@ -205,9 +191,9 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
   {
     double H[21];
     UNROLL for (int i = 0; i < 21; i++) H[i] = Pk[i];
-    VJP_ROWS(r)
+    GRAD_ROWS(r)
       row_outer<r>(rho[ri_], t2, H);
-    VJP_END
+    GRAD_END
     if (!act) {   // (a lane without a segment: a decoupled identity)
       UNROLL for (int i = 0; i < 21; i++) H[i] = 0.0;
       UNROLL for (int i = 0; i < 6; i++) H[SYM(i, i)] = 1.0;
@@ -260,12 +246,12 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
 
   // ---- passes of the method of multipliers ----
   double v[6];   // v in control-point space (this segment)
-  for (int pass = 0; pass < VJP_PASSES; ++pass) {
+  for (int pass = 0; pass < GRAD_PASSES; ++pass) {
     double h[6];
     UNROLL for (int i = 0; i < 6; i++) h[i] = xb[i];
-    VJP_ROWS(r)
+    GRAD_ROWS(r)
       row_scatter<r>(-w[ri_], t, h);
-    VJP_END
+    GRAD_END
     if (!act) { UNROLL for (int i = 0; i < 6; i++) h[i] = 0.0; }
     double u[3];
     {
@@ -306,9 +292,9 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
     UNROLL for (int i = 0; i < 3; i++) { const double vv = dpp_prev(X[i]); Xp[i] = first ? 0.0 : vv; }   // (the initial state is given)
     U_apply(nm, Xp, v[0], v[1], v[2]);
     V_apply(nm, X, v[3], v[4], v[5]);
-    VJP_ROWS(r)
+    GRAD_ROWS(r)
       w[ri_] += rho[ri_] * row_dot<r>(v, t);
-    VJP_END
+    GRAD_END
   }
   if (!act) { UNROLL for (int i = 0; i < 6; i++) v[i] = 0.0; }
 
@@ -319,7 +305,7 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
   double g_alo = 0.0, g_ahi = 0.0, g_jlo = 0.0, g_jhi = 0.0;
   double to_next[4] = {0.0, 0.0, 0.0, 0.0};   // amounts for the next segment's plo0, phi0, vlo[0], vhi[0]
   double own0[4] = {0.0, 0.0, 0.0, 0.0};      // (this segment's own row-0 / row-6 amounts come from the previous lane)
-  VJP_ROWS(r)
+  GRAD_ROWS(r)
     const double wl = side[ri_] < 0 ? w[ri_] : 0.0, wu = side[ri_] > 0 ? w[ri_] : 0.0;
     if constexpr (r < 6) {
       if (r == 5 && nx_plo) to_next[0] += wl; else { g_lb += wl * lo0_b; g_ls += wl * (lo0_s + (double)r * lod_s); }
@@ -333,7 +319,7 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
     } else {
       g_jlo += wl * jlo_f; g_jhi += wu * jhi_f;
     }
-  VJP_END
+  GRAD_END
   UNROLL for (int i = 0; i < 4; i++) { const double vv = dpp_prev(to_next[i]); own0[i] = first ? 0.0 : vv; }
   g_lb += own0[0] * lo0_b; g_ls += own0[0] * lo0_s;
   g_ub += own0[1] * hi0_b; g_us += own0[1] * hi0_s;
@@ -380,9 +366,9 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
       UNROLL for (int j = 0; j < 6; j++) s += HSYM(Pk, i, j) * v[j];
       r6[i] = xb[i] - s;
     }
-    VJP_ROWS(r)
+    GRAD_ROWS(r)
       row_scatter<r>(-w[ri_], t, r6);
-    VJP_END
+    GRAD_END
     UT_apply(nm, r6[0], r6[1], r6[2], g_init);
   }
 
@@ -426,6 +412,8 @@ __global__ __launch_bounds__(64) void vjp_kernel(const VjpArgs a) {
     gsh[12 + 4 * axis] = ok ? s1.b : 0.0; gsh[13 + 4 * axis] = ok ? s1.c : 0.0;
     gsh[14 + 4 * axis] = ok ? s1.d : 0.0; gsh[15 + 4 * axis] = ok ? s2.a : 0.0;
   }
+#undef VLO
+#undef VUP
 }
 
 }  // namespace btrapz
