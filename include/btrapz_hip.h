@@ -394,7 +394,19 @@ int btrapz_multi_download(btrapz_multi *m, double *ctrl, double *cost, int *stat
 
 /* Bernstein sampling (solve_3d.cc:1279-1392) of nsel selected candidates on device.
  *   sel [nsel] candidate indices; t taken from seg; out [nsel][6][max_points]
- *   (s, ds, dds, l, dl, ddl); npoints [nsel].  Device pointers. */
+ *   (s, ds, dds, l, dl, ddl); npoints [nsel].  Device pointers.
+ * Defined cases (also of btrapz_sample_ragged_device; held by tests/test_gpu_sample_eval_forward.py):
+ *   npoints[j] is the reference's count, an int accumulated with += t_k / delta in double (solve_3d.cc:1279-1282).  It is
+ *     at least 1 + total, total = the sum of (int)(t_k / delta), and larger where a quotient lies one ulp below a whole
+ *     number (0.3 / 0.1): what the reference aborts on (:1407) and btrapz_traj_cost_device does not score.  It does not
+ *     depend on max_points.
+ *   Only the entries 0 .. min(1 + total, max_points) - 1 of each of the six rows are written: entry 0 is init, entry
+ *     1 + i the i-th Bernstein sample (position = the Bernstein sum times t_k, velocity unscaled, acceleration over t_k; a
+ *     segment shorter than delta has no sample).  The rest of a row -- the entries from 1 + total to npoints - 1 when
+ *     the count runs ahead included -- keeps what the caller put there.
+ *   A selection outside [0, B), or a candidate whose segment count is outside 1 .. seg_stride, gives npoints = 0 and
+ *     an untouched row.  A selection named twice gives two identical rows.
+ *   Slots of seg and ctrl beyond a candidate's own count are not read. */
 int btrapz_sample_device(btrapz_ctx *ctx, int B, int S, double delta, const double *seg,
                          const double *init, const double *ctrl, int nsel,
                          const long long *sel, int max_points, double *out, int *npoints,
@@ -552,7 +564,9 @@ int btrapz_prism_corridor_batch_device(btrapz_ctx *ctx, int variant, int B, int 
                                        int seg_stride, double *seg, int *seg_count, double *ref_end,
                                        double *dl_bounds, int *n_strips, void *stream);
 
-/* btrapz_sample_device for ragged batches (seg_count may be NULL: every candidate has seg_stride). */
+/* btrapz_sample_device for ragged batches (seg_count may be NULL: every candidate has seg_stride, and the call gives the
+ * bits of btrapz_sample_device, as it does with every count equal to seg_stride).  Candidate b's control points lie at
+ * ctrl[b][0, 6 S_b) (s axis) and [6 S_b, 12 S_b) (l axis), S_b its own count.  Defined cases: as btrapz_sample_device. */
 int btrapz_sample_ragged_device(btrapz_ctx *ctx, int B, int seg_stride, const int *seg_count,
                                 double delta, const double *seg, const double *init,
                                 const double *ctrl, int nsel, const long long *sel, int max_points,
@@ -757,7 +771,14 @@ int btrapz_traj_cost_vjp_device(btrapz_ctx *ctx, const btrapz_shared *sets, int 
  * start of candidate b's horizon (Bezier evaluation of solve_3d.cc:1366-1388; beyond the last segment the
  * end state is extrapolated at constant velocity).  With times = shift + the cumulative durations of the
  * NEXT step's segments this is x0 of btrapz_warm.  times [B][n_times], x [B][2][n_times][3]; seg_count may
- * be NULL. */
+ * be NULL.
+ * Defined cases (held by tests/test_gpu_sample_eval_forward.py): a time that is not > 0, NaN included, gives the start of
+ * the first segment; a time belongs to the segment the walk `while (k < S - 1 && rem > t_k) rem -= t_k` leaves it in (in
+ * double: a time on a joint is the earlier segment's end where the subtractions leave rem == t_k, the later one's start
+ * where they leave it above); beyond the horizon p continues at the end velocity, v is
+ * the end velocity and a is 0; a candidate whose segment count is outside 1 .. seg_stride gets NaN in all six entries of
+ * every time, and no other candidate's entries are touched; slots of seg and ctrl beyond a candidate's own count (control
+ * points at [0, 6 S_b) and [6 S_b, 12 S_b)) are not read. */
 int btrapz_eval_states_device(btrapz_ctx *ctx, int B, int seg_stride, const int *seg_count,
                               const double *seg, const double *ctrl, int n_times, const double *times,
                               double *x, void *stream);

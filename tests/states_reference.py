@@ -50,8 +50,9 @@ def samples_per_segment(t, delta):
 
 
 # ---- state evaluation -------------------------------------------------------------------------------------------------
-def locate(t, time):
-    """eval_states_kernel's branches for one time: (k, tau, over, clamped)."""
+def walk(t, time):
+    """eval_states_kernel's float walk for one time: (k, rem, over, clamped) -- the segment, the time left inside it,
+    the time beyond the horizon (0 inside it) and whether the time was not > 0."""
     S = len(t)
     rem = time
     clamped = not (rem > 0.0)
@@ -62,6 +63,12 @@ def locate(t, time):
         rem -= t[k]
         k += 1
     over = rem - t[k] if rem > t[k] else 0.0
+    return k, rem, over, clamped
+
+
+def locate(t, time):
+    """eval_states_kernel's branches for one time: (k, tau, over, clamped)."""
+    k, rem, over, clamped = walk(t, time)
     tau = 1.0 if over > 0.0 else rem / t[k]
     return k, tau, over, clamped
 
