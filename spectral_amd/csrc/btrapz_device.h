@@ -296,6 +296,7 @@ __global__ void sets_scatter_kernel(int B, int seg_stride, const int *seg_count,
 __global__ void ipm_solve_long_kernel(const KernelArgs a, const double *__restrict__ mqm);          // 65..256 segments: one axis problem per workgroup
 __global__ void ipm_solve_long_warm_kernel(const KernelArgs a, const double *__restrict__ mqm);     // + btrapz_warm (btrapz_solve_long_warm_device)
 __global__ void ipm_solve_long_elastic_kernel(const KernelArgs a, const double *__restrict__ mqm);  // rescue pass of the long form (<= 192 segments)
+__global__ void ipm_solve_long_rescue_kernel(const KernelArgs a, const double *__restrict__ mqm);   // ... of 193..256 segments (btrapz_solve_long_rescue_device)
 __global__ void rescue_keys_kernel(int B, int S, const int *seg_count, const int *axis_status, int *keys, int all);
 __global__ void rescue_init_kernel(int B, int S, const int *seg_count, double *axis_obj, int *axis_status, int *axis_iters);
 struct MqmWeights { double w[2][4]; };   // [axis][ref, dref, acc, jerk]

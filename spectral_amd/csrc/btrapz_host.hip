@@ -19,6 +19,7 @@
 #include "../../include/btrapz_hip_schedule.h"
 #include "../../include/btrapz_hip_check.h"
 #include "../../include/btrapz_hip_long.h"
+#include "../../include/btrapz_hip_long_rescue.h"
 #include "../../include/btrapz_hip_long_grad.h"
 #include "btrapz_long_grad.h"
 #include "prism_core.h"
@@ -621,6 +622,7 @@ struct Solve {
   KernelArgs a;
   int elastic; bool compact, warm_kernel;
   bool long_warm;                   // btrapz_solve_long_warm_device: candidates of 65..256 segments take ipm_solve_long_warm_kernel
+  bool long_rescue;                 // btrapz_solve_long_rescue_device: ... and have their rescue pass up to 256 segments, listed ones too
   unsigned blocks;                  // wavefronts of the one-launch packed / lean form
 };
 
@@ -890,7 +892,7 @@ static int solve_main_launch(Solve &s, Form &f) {
   q.elastic = s.elastic; q.max_iter = a.max_iter; q.unc_start = a.unc_start; q.resident_waves = c->resident_waves; q.blocks = s.blocks;
   solve_requests(s.opt, q);
   f = choose_form(q);
-  if (f.long_form && (a.order || (s.warm_kernel && !s.long_warm) || s.elastic == 2 || (s.elastic == 1 && S > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE))) {
+  if (f.long_form && (a.order || (s.warm_kernel && !s.long_warm) || s.elastic == 2 || (s.elastic == 1 && S > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE && !s.long_rescue))) {
     c->err = "more than 64 segments: uniform cold solve only, rescue pass (elastic = 1) up to 192 segments";
     return BTRAPZ_EINVAL;
   }
@@ -951,16 +953,25 @@ static KernelArgs rescue_arguments(const KernelArgs &a) {
   return e;
 }
 
+// Rescue launch of the long form over n candidates of `segs` segments -- a (with a.order == nullptr: the uniform batch in
+// memory order; else the list of solve_long_candidates) are the arguments of the plain launch it follows.  One workgroup
+// per axis problem again; those whose problem did not stall leave at once.  Up to 192 segments three wavefronts, beyond
+// (btrapz_solve_long_rescue_device) the four-wavefront kernel: a width is served by ONE kernel, whichever path leads to it.
+static void launch_long_rescue(btrapz_ctx *c, hipStream_t stream, const KernelArgs &a, unsigned n, int segs) {
+  const KernelArgs e = rescue_arguments(a);
+  auto kernel = segs > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE ? ipm_solve_long_rescue_kernel : ipm_solve_long_elastic_kernel;
+  hipLaunchKernelGGL(kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, stream, e, (const double *)c->d_mqm);
+}
+
 // Step: the rescue pass (btrapz_options.elastic) of the long form and of the packed form.
 static int solve_rescue_pass(Solve &s, bool long_form) {
   btrapz_ctx *c = s.c; const int B = s.B, S = s.S;
   if (long_form) {
-    // Rescue pass of the long form: one workgroup per axis problem again; those whose problem did not stall leave at once
     HIPCHK(c, hipMemsetAsync(c->d_axis_viol, 0, sizeof(double) * 8 * (size_t)B, s.stream));
     c->viol_valid = (size_t)B;
-    KernelArgs e = rescue_arguments(s.a);
+    KernelArgs e = s.a;
     e.order = nullptr;
-    hipLaunchKernelGGL(ipm_solve_long_elastic_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, s.stream, e, (const double *)c->d_mqm);
+    launch_long_rescue(c, s.stream, e, (unsigned)B, S);
     HIPCHK(c, hipGetLastError());
     return BTRAPZ_OK;
   }
@@ -998,7 +1009,7 @@ static int solve_rescue_pass(Solve &s, bool long_form) {
 static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_options *opt, const btrapz_warm *warm,
                         int B, int S, const int *seg_count, const double *seg, const double *init, const double *ref_end,
                         const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters, void *stream_,
-                        bool long_warm = false) {
+                        bool long_warm = false, bool long_rescue = false) {
   if (!c) return BTRAPZ_EINVAL;
   if (!sh || B < 1 || S < 1 || (!seg_count && S > BTRAPZ_MAX_SEGMENTS_LONG) || !seg || !init || !ref_end || !dl_bounds ||
       !ctrl || !cost || !status) {
@@ -1007,7 +1018,7 @@ static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_opt
   }
   if (!options_ok(c, opt)) return BTRAPZ_EINVAL;
   Solve s;
-  s.c = c; s.stream = (hipStream_t)stream_; s.opt = opt; s.B = B; s.S = S; s.seg_count = seg_count; s.long_warm = long_warm;
+  s.c = c; s.stream = (hipStream_t)stream_; s.opt = opt; s.B = B; s.S = S; s.seg_count = seg_count; s.long_warm = long_warm; s.long_rescue = long_rescue;
   TRY(ws_open(c, s.stream));
   TRY(ensure_axis_ws(c, 2 * (size_t)B));
   TRY(solve_weights_table(c, sh, s.stream));
@@ -1027,11 +1038,15 @@ static int solve_common(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_opt
   Form f;
   TRY(solve_main_launch(s, f));
   if (s.elastic) TRY(solve_rescue_pass(s, f.long_form));
-  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && (!s.warm_kernel || long_warm) && s.elastic == 0) {
-    // (a warm ragged solve leaves its long candidates at BTRAPZ_NO_CORRIDOR; btrapz_solve_long_warm_device solves them warm)
-    auto kernel = s.warm_kernel ? ipm_solve_long_warm_kernel : ipm_solve_long_kernel;
+  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && (!s.warm_kernel || long_warm) && (s.elastic == 0 || (long_rescue && s.elastic == 1))) {
+    // (a warm ragged solve leaves its long candidates at BTRAPZ_NO_CORRIDOR; btrapz_solve_long_warm_device solves them warm.
+    //  With a rescue pass -- btrapz_solve_long_rescue_device -- a count's plain launch is followed by its rescue launch over
+    //  the same list (the packed rescue pass above has zeroed d_axis_viol), and a count beyond 192 takes the kernel the
+    //  uniform call of that width takes: the warm instantiation, whatever the start.)
     auto launch = [&](const KernelArgs &l, unsigned n, int segs) {
-      hipLaunchKernelGGL(kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, s.stream, l, (const double *)c->d_mqm);
+      const bool warm_k = s.warm_kernel || (long_rescue && segs > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE);
+      hipLaunchKernelGGL(warm_k ? ipm_solve_long_warm_kernel : ipm_solve_long_kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, s.stream, l, (const double *)c->d_mqm);
+      if (s.elastic) launch_long_rescue(c, s.stream, l, n, segs);
     };
     TRY(solve_long_candidates(c, s.stream, a, seg_count, launch));
   }
@@ -1087,6 +1102,46 @@ BTRAPZ_EXPORT int btrapz_solve_long_warm_device(btrapz_ctx *c, const btrapz_shar
   if (warm) { w = *warm; w.hint = nullptr; }
   return solve_common(c, sh, opt, warm ? &w : nullptr, B, seg_stride, seg_count, seg, init, ref_end, dl_bounds, ctrl, cost,
                       status, iters, stream, true);
+}
+
+// btrapz_solve_long_warm_device with the rescue pass (include/btrapz_hip_long_rescue.h).  Each case is handed to the path
+// that serves it already wherever there is one -- the answer is then that path's, bit for bit: without a rescue pass the call
+// above; up to 64 slots btrapz_solve_warm_device; a uniform batch of 65..192 segments without a start btrapz_solve_batch_device.
+// What is left -- a uniform batch beyond 192 segments or with a start, a ragged record with slots beyond 64 -- is
+// solve_common with long_rescue.
+BTRAPZ_EXPORT int btrapz_solve_long_rescue_device(btrapz_ctx *c, const btrapz_shared *sh, const btrapz_options *opt,
+                                               const btrapz_warm *warm, int B, int seg_stride, const double *seg,
+                                               const int *seg_count, const double *init, const double *ref_end,
+                                               const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters,
+                                               void *stream) {
+  if (!c) return BTRAPZ_EINVAL;
+  const char *missing = !sh ? "shared" : !seg ? "seg" : !init ? "init" : !ref_end ? "ref_end" : !dl_bounds ? "dl_bounds" : !ctrl ? "ctrl" :
+                        !cost ? "cost" : !status ? "status" : B < 1 ? "B" : seg_stride < 1 ? "seg_stride" : nullptr;
+  if (missing) {
+    c->err = std::string("invalid argument: btrapz_solve_long_rescue_device: ") + missing + (B < 1 || seg_stride < 1 ? " < 1" : " is NULL");
+    return BTRAPZ_EINVAL;
+  }
+  if (!options_ok(c, opt)) return BTRAPZ_EINVAL;
+  if (!opt || opt->elastic == 0)
+    return btrapz_solve_long_warm_device(c, sh, opt, warm, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost,
+                                         status, iters, stream);
+  if (seg_stride > BTRAPZ_MAX_SEGMENTS_LONG) {
+    c->err = "invalid argument: seg_stride > BTRAPZ_MAX_SEGMENTS_LONG";
+    return BTRAPZ_EINVAL;
+  }
+  if (seg_stride <= BTRAPZ_MAX_SEGMENTS)
+    return solve_common(c, sh, opt, warm, B, seg_stride, seg_count, seg, init, ref_end, dl_bounds, ctrl, cost, status, iters, stream);
+  if (opt->elastic != 1) {
+    c->err = "invalid argument: btrapz_options.elastic beyond 64 segments: 0 or 1 (elastic rows for every candidate, 2, are not served)";
+    return BTRAPZ_EINVAL;
+  }
+  const bool start = warm && (warm->x0 || warm->lam0 || warm->lam_out);
+  if (!seg_count && seg_stride <= BTRAPZ_MAX_SEGMENTS_LONG_RESCUE && !start)
+    return solve_common(c, sh, opt, nullptr, B, seg_stride, nullptr, seg, init, ref_end, dl_bounds, ctrl, cost, status, iters, stream);
+  btrapz_warm w;   // (the hint orders the packed forms' wavefronts: it says nothing to one problem per workgroup)
+  if (warm) { w = *warm; w.hint = nullptr; }
+  return solve_common(c, sh, opt, warm ? &w : nullptr, B, seg_stride, seg_count, seg, init, ref_end, dl_bounds, ctrl, cost,
+                      status, iters, stream, true, true);
 }
 
 // ---- entry points that take parameter sets: the sets solve, its VJP and JVP, traj_cost ---------------------------------

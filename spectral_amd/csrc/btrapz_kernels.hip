@@ -1393,12 +1393,30 @@ __global__ __launch_bounds__(256) void ipm_solve_long_warm_kernel(const KernelAr
   ipm_solve_body<true, false, false, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63, wgs, wv);
 }
 // ... and its rescue pass (btrapz_options.elastic): the workgroups of the axis problems that stalled solve them again with
-// elastic rows, the others leave at once.  Up to three wavefronts (192 segments): the 18-row LDS columns of a fourth do
-// not fit the CU.
+// elastic rows, the others leave at once.  Workgroup w: axis w & 1 of candidate w >> 1 -- in memory order, or, with a
+// list (a.order, a.bucket_S entries: the long candidates of one segment count of a ragged batch), of the list.
+__device__ __forceinline__ bool long_rescue_stalled(const KernelArgs &a) {   // (the same for every thread of the workgroup)
+  const int w = (int)blockIdx.x;
+  const long long prob = a.order ? 2LL * a.order[w >> 1] + (w & 1) : (long long)w;
+  return a.axis_status[prob] == BTRAPZ_MAX_ITER_REACHED;
+}
+// Up to three wavefronts (192 segments): 3 x 76 LDS rows and the workgroup's block, 125 KB.
 __global__ __launch_bounds__(192) void ipm_solve_long_elastic_kernel(const KernelArgs a, const double *__restrict__ mqm) {
   __shared__ double lds[3][lds_rows<true>()][64];
   __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
-  if (a.axis_status[blockIdx.x] != BTRAPZ_MAX_ITER_REACHED) return;   // (the same for every thread of the workgroup)
+  if (!long_rescue_stalled(a)) return;
+  const int wv = (int)threadIdx.x >> 6;
+  ipm_solve_body<false, false, true, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63, wgs, wv);
+}
+// Four wavefronts (193..256 segments; btrapz_solve_long_rescue_device).  lds_rows<true>() = 4 x 18 + 4 rows per wavefront
+// would need 4 x 76 x 512 + (8 + 4 x 256) x 8 = 163 904 B, 64 B more than the CU's 160 KB -- but the last four are the
+// reduction rows L_RED, and the long form never touches them: reduce4<MULTI = true> and the duration prefix of the set-up
+// go through wgs, the other users of lds[L_RED] (the packed reductions, QUEUE's refill, CAPPED's slot draw) are not
+// instantiated with MULTI.  Without them: 4 x 72 x 512 + 8 256 = 155 712 B.  The workgroup has its CU to itself.
+__global__ __launch_bounds__(256) void ipm_solve_long_rescue_kernel(const KernelArgs a, const double *__restrict__ mqm) {
+  __shared__ double lds[4][4 * rows_kept<true>()][64];
+  __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
+  if (!long_rescue_stalled(a)) return;
   const int wv = (int)threadIdx.x >> 6;
   ipm_solve_body<false, false, true, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63, wgs, wv);
 }

@@ -21,6 +21,7 @@
 #include <sched.h>
 
 #include "btrapz_device.h"
+#include "../../include/btrapz_hip_long_rescue.h"
 #include "corridor.hpp"
 #include "traj_cost.h"
 
@@ -323,13 +324,17 @@ double run_find_traj(int variant, const TrajInput &in, const Params *p, TrajResu
     if (hipMemcpyAsync(s_in, h_in, (n_in + 1) * 8, hipMemcpyHostToDevice, me->stream) != hipSuccess) return FAIL;
     btrapz_options opt;
     btrapz_options_init(&opt);
-    // (the long form has its rescue pass up to 192 segments; beyond, the plain solve decides)
-    const bool rescue = el.on && (!long_form || S <= BTRAPZ_MAX_SEGMENTS_LONG_RESCUE);
+    // (the long form has its rescue pass up to 256 segments, all it solves: beyond 192 through the entry point of
+    //  btrapz_hip_long_rescue.h, which the batched one refuses there)
+    const bool rescue = el.on;
     opt.elastic = rescue ? 1 : 0; opt.elastic_tol = el.tol;
     double *s_viol = s_out + n_out;
     double h_viol[4] = {0.0, 0.0, 0.0, 0.0};
-    if (btrapz_solve_batch_device(ctx, &sh, &opt, 1, S, s_in, s_init, s_init + 6, s_init + 8, s_out + 3, s_out, s_status,
-                                  s_status + 1, me->stream) != BTRAPZ_OK ||
+    const bool beyond = rescue && long_form && S > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE && S <= BTRAPZ_MAX_SEGMENTS_LONG;
+    if ((beyond ? btrapz_solve_long_rescue_device(ctx, &sh, &opt, nullptr, 1, S, s_in, nullptr, s_init, s_init + 6, s_init + 8, s_out + 3,
+                                                  s_out, s_status, s_status + 1, me->stream)
+                : btrapz_solve_batch_device(ctx, &sh, &opt, 1, S, s_in, s_init, s_init + 6, s_init + 8, s_out + 3, s_out, s_status,
+                                            s_status + 1, me->stream)) != BTRAPZ_OK ||
         btrapz_sample_device(ctx, 1, S, in.delta, s_in, s_init, s_out + 3, 1, s_sel, max_points, s_out + 3 + 12 * S, s_np,
                              me->stream) != BTRAPZ_OK ||
         (rescue && btrapz_rescue_violations_device(ctx, 1, s_viol, me->stream) != BTRAPZ_OK)) {

@@ -262,6 +262,12 @@ PROTOTYPES_LONG = {
 }
 EXPORTS_LONG = tuple(PROTOTYPES_LONG)
 
+# Every function of include/btrapz_hip_long_rescue.h, the same way (tests/test_long_rescue_goldens.py holds it to that header).
+PROTOTYPES_LONG_RESCUE = {
+    "btrapz_solve_long_rescue_device": PROTOTYPES_LONG["btrapz_solve_long_warm_device"],
+}
+EXPORTS_LONG_RESCUE = tuple(PROTOTYPES_LONG_RESCUE)
+
 # Every function of include/btrapz_hip_long_grad.h, the same way (tests/test_long_grad_abi.py holds it to that header).
 PROTOTYPES_LONG_GRAD = {
     "btrapz_solve_long_vjp_device": (_i, [_vp, _sh, _i, _vp, _i, _i] + _ragged + [_vp, _vp, _vp, _vp, _vp, C.POINTER(CGrads), _vp]),
@@ -349,7 +355,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_GRAD.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -538,6 +544,15 @@ class Context:
         """btrapz_solve_long_warm_device (include/btrapz_hip_long.h): solve_warm_device with seg_stride up to 256 -- the
         candidates of 65..256 segments are warm-started and keep their multipliers too.  elastic != 0 is refused."""
         self._warm_call("btrapz_solve_long_warm_device", B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl,
+                        cost, status, iters, _warm(x0, lam0, lam_out, mu0, smin, hint), stream,
+                        _options(max_iter, eps, elastic, elastic_tol, lean=lean))
+
+    def solve_long_rescue_device(self, B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
+                                 iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, stream=None, max_iter=0,
+                                 eps=0.0, hint=None, elastic=1, elastic_tol=0.0, lean=0):
+        """btrapz_solve_long_rescue_device (include/btrapz_hip_long_rescue.h): solve_long_warm_device with the rescue pass
+        (elastic 0 or 1) -- uniform batches up to 256 segments and the long candidates of a ragged record too."""
+        self._warm_call("btrapz_solve_long_rescue_device", B, seg_stride, shared, seg, seg_count, init, ref_end, dl_bounds, ctrl,
                         cost, status, iters, _warm(x0, lam0, lam_out, mu0, smin, hint), stream,
                         _options(max_iter, eps, elastic, elastic_tol, lean=lean))
 

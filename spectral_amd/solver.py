@@ -166,6 +166,16 @@ class BatchSolver:
         return self._warm_solve(self.ctx.solve_long_warm_device, self._record(dbatch_or_rec), shared, warm, keep_multipliers, out,
                                 max_iter=max_iter, eps=eps)
 
+    def solve_long_rescue(self, dbatch_or_rec, shared, warm=None, keep_multipliers=False, max_iter=0, eps=0.0, out=None, elastic=1,
+                          elastic_tol=0.0):
+        """solve_long with the rescue pass (btrapz_solve_long_rescue_device; elastic: 0 or 1, elastic_tol:
+        btrapz_options.elastic_tol, 0 = the default): a candidate of up to 256 segments that stalls is solved again with
+        elastic rows -- the long candidates of a ragged record too -- and comes back with status 2 where its least violation
+        is within the tolerance.  "lam" of a rescued candidate is the stalled solve's.  elastic = 0 is solve_long, bit for
+        bit.  (A method of its own: solve_long's signature is part of its contract.)"""
+        return self._warm_solve(self.ctx.solve_long_rescue_device, self._record(dbatch_or_rec), shared, warm, keep_multipliers, out,
+                                max_iter=max_iter, eps=eps, elastic=elastic, elastic_tol=elastic_tol)
+
     def prepare(self, dbatch, shared, out=None, **options):
         """solve(dbatch, shared, **options) prepared once: returns (call, out) where call() launches the solve on the
         stream that is current NOW and `out` is the dict of device tensors it fills (cold solves only)."""
