@@ -168,7 +168,9 @@ enum {
 #define BTRAPZ_MAX_SEGMENTS_LONG_RESCUE 192
 
 /* Weights (Params) and limits (input-file header, trp_wrapper.cpp:59-64) shared by all
- * candidates of a batch. */
+ * candidates of a batch.  Every limit is a (lower, upper) pair in the trajectory's own units (m/s^2, m/s^3), each side
+ * applied as given -- lower <= value <= upper, nothing symmetrised, either side may be tightened alone; dds is clamped
+ * to [-1000, 1000] (solve_3d.cc:836,843-844). */
 typedef struct btrapz_shared {
   double w_s[4]; /* weight_s_ref, weight_ds_ref, s_acc_weight, s_jerk_weight */
   double w_l[4]; /* weight_l_ref, weight_dl_ref, l_acc_weight, l_jerk_weight */
