@@ -288,6 +288,13 @@ __global__ void ipm_solve_lean_sets_ordered_kernel(const KernelArgs a, const dou
 __global__ void ipm_solve_lean_sets_warm_ordered_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, int n_keys);
 __global__ void ipm_solve_sets_split_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, const int *set_index, int n_sets);
 __global__ void ipm_solve_long_sets_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, const int *set_index, int n_sets);
+// btrapz_solve_long_sets_device (btrapz_kernels.hip): warm starts beyond 64 segments and the rescue pass, with sets
+__global__ void ipm_solve_long_warm_sets_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, const int *set_index, int n_sets);
+__global__ void ipm_solve_elastic_sets_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, int n_keys);   // tables [2][3 n_keys + 2], lists [2][B]
+__global__ void ipm_solve_long_elastic_sets_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, const int *set_index, int n_sets);
+__global__ void ipm_solve_long_rescue_sets_kernel(const KernelArgs a, const double *__restrict__ mqm, const Shared *sets, const int *set_index, int n_sets);
+// masked[axis][b] = set_index[b] where that axis problem stalled, else -1: the "set index" the bucket kernels list the rescue pass by
+__global__ void sets_rescue_index_kernel(int B, const int *set_index, const int *axis_status, int *masked);
 __global__ void sets_hist_kernel(int B, int seg_stride, const int *seg_count, const int *set_index, int n_sets, int n_keys, int *meta);
 __global__ void sets_prefix_kernel(int n_keys, int fixed_S, int *meta);
 __global__ void sets_scatter_kernel(int B, int seg_stride, const int *seg_count, const int *set_index, int n_sets, int n_keys,

@@ -20,6 +20,7 @@
 #include "../../include/btrapz_hip_check.h"
 #include "../../include/btrapz_hip_long.h"
 #include "../../include/btrapz_hip_long_rescue.h"
+#include "../../include/btrapz_hip_long_sets.h"
 #include "../../include/btrapz_hip_long_grad.h"
 #include "btrapz_long_grad.h"
 #include "prism_core.h"
@@ -184,6 +185,7 @@ struct btrapz_ctx {
   Buf<double> d_argmin_cost{bufs}; Buf<long long> d_argmin_idx{bufs};   // partial arg-mins (one capacity, idx allocated last)
   Buf<double> d_topk_cost{bufs}; Buf<long long> d_topk_idx{bufs};       // partial K-best lists (btrapz_select.hip), the same way
   // rescue pass (btrapz_options.elastic): keys [2][B], per-axis candidate lists [2][B], bucket tables [2][198]
+  // (with parameter sets, sets_rescue_pass: masked set indices [2][B], lists [2][B], tables [2][3 n_keys + 2])
   Buf<int> d_rescue{bufs};
   Buf<int> d_rescue_meta{bufs};
   // staging for the host-pointer wrapper
@@ -957,10 +959,18 @@ static KernelArgs rescue_arguments(const KernelArgs &a) {
 // memory order; else the list of solve_long_candidates) are the arguments of the plain launch it follows.  One workgroup
 // per axis problem again; those whose problem did not stall leave at once.  Up to 192 segments three wavefronts, beyond
 // (btrapz_solve_long_rescue_device) the four-wavefront kernel: a width is served by ONE kernel, whichever path leads to it.
-static void launch_long_rescue(btrapz_ctx *c, hipStream_t stream, const KernelArgs &a, unsigned n, int segs) {
+// set_index (btrapz_solve_long_sets_device): the same two kernels with SETS, every workgroup reading its candidate's set.
+static void launch_long_rescue(btrapz_ctx *c, hipStream_t stream, const KernelArgs &a, unsigned n, int segs,
+                               const int *set_index = nullptr, int n_sets = 0) {
   const KernelArgs e = rescue_arguments(a);
+  const dim3 grid(2u * n), block(64u * (unsigned)((segs + 63) / 64));
+  if (set_index) {
+    auto kernel = segs > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE ? ipm_solve_long_rescue_sets_kernel : ipm_solve_long_elastic_sets_kernel;
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, e, (const double *)c->d_mqm_sets, (const Shared *)c->d_sets, set_index, n_sets);
+    return;
+  }
   auto kernel = segs > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE ? ipm_solve_long_rescue_kernel : ipm_solve_long_elastic_kernel;
-  hipLaunchKernelGGL(kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, stream, e, (const double *)c->d_mqm);
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, e, (const double *)c->d_mqm);
 }
 
 // Step: the rescue pass (btrapz_options.elastic) of the long form and of the packed form.
@@ -1217,8 +1227,9 @@ static int sets_tables(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, hip
 // on the device by (set, segment count) -- btrapz_sets.hip -- and solved in ONE launch of an ordered instantiation whose
 // wavefronts each hold one set (ipm_solve_*sets*_kernel).  The split form (few candidates) and the long form (65..256
 // segments; the long candidates of a cold ragged batch) hold one candidate per wavefront / workgroup and read its set
-// themselves.  The form comes from choose_form, as for solve_common; the rescue pass, the two-launch solve and the
-// pre-pass are not served here, and the requests are those of btrapz_options (no environment).
+// themselves.  The form comes from choose_form, as for solve_common; the two-launch solve and the pre-pass are not served
+// here, the rescue pass and warm starts beyond 64 segments through btrapz_solve_long_sets_device only, and the requests are
+// those of btrapz_options (no environment).
 
 // The packed / lean launch of a sets batch: candidates bucketed by key -- set (uniform) or 64 set + 64 - segment count
 // (ragged) -- then one launch over the buckets.
@@ -1252,6 +1263,108 @@ static int launch_sets_buckets(btrapz_ctx *c, hipStream_t stream, KernelArgs &a,
   return BTRAPZ_OK;
 }
 
+// The rescue pass of a sets solve (btrapz_solve_long_sets_device, opt->elastic == 1), after its plain launch with arguments a.
+// Long form: solve_rescue_pass's launch with SETS.  Up to 64 segments: the stalled axis problems are listed per axis and
+// bucketed by (set, segment count) with the bucket kernels of the plain launch -- given, in place of set_index, the set of
+// the candidates whose axis problem stalled and -1 for the others -- so that a wavefront of the elastic instantiation holds
+// one set.  Tables: [2][3 n_keys + 2] in d_rescue_meta (n_keys = 64 n_sets for a ragged record: 1.5 MB at 1 024 sets);
+// masked indices [2][B] and lists [2][B] in d_rescue.
+static int sets_rescue_pass(btrapz_ctx *c, hipStream_t stream, const KernelArgs &a, const int *seg_count, const int *set_index,
+                            int n_sets, bool long_form) {
+  const int B = a.B, S = a.S;
+  HIPCHK(c, hipMemsetAsync(c->d_axis_viol, 0, sizeof(double) * 8 * (size_t)B, stream));
+  c->viol_valid = (size_t)B;
+  if (long_form) {
+    KernelArgs e = a;
+    e.order = nullptr;
+    launch_long_rescue(c, stream, e, (unsigned)B, S, set_index, n_sets);
+    HIPCHK(c, hipGetLastError());
+    return BTRAPZ_OK;
+  }
+  const int n_keys = (seg_count ? 64 : 1) * n_sets;
+  const size_t per_axis = 3 * (size_t)n_keys + 2;
+  GROW(c, d_rescue, sizeof(int) * 4 * (size_t)B);
+  GROW(c, d_rescue_meta, sizeof(int) * 2 * per_axis);
+  int *masked = c->d_rescue, *lists = c->d_rescue + 2 * (size_t)B, *meta = c->d_rescue_meta;
+  const unsigned nb = (unsigned)((B + 255) / 256);
+  hipLaunchKernelGGL(sets_rescue_index_kernel, dim3(nb), dim3(256), 0, stream, B, set_index, (const int *)c->d_axis_status, masked);
+  HIPCHK(c, hipMemsetAsync(meta, 0, sizeof(int) * 2 * per_axis, stream));
+  for (int ax = 0; ax < 2; ax++) {
+    int *m = meta + (size_t)ax * per_axis;
+    const int *idx = masked + (size_t)ax * B;
+    hipLaunchKernelGGL(sets_hist_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, idx, n_sets, n_keys, m);
+    hipLaunchKernelGGL(sets_prefix_kernel, dim3(1), dim3(1024), 0, stream, n_keys, seg_count ? 0 : S, m);
+    hipLaunchKernelGGL(sets_scatter_kernel, dim3(nb), dim3(256), 0, stream, B, S, seg_count, idx, n_sets, n_keys, m,
+                       lists + (size_t)ax * B, (double *)nullptr, (int *)nullptr, (int *)nullptr);
+  }
+  HIPCHK(c, hipGetLastError());
+  KernelArgs e = rescue_arguments(a);
+  e.order = lists; e.seg_count = seg_count; e.cand_prefix = meta; e.wave_prefix = meta + n_keys + 1;
+  e.bucket_S = seg_count ? 0 : S;
+  // (wavefront pairs per axis: launch_sets_buckets' bound)
+  const int gpw_min = seg_count ? 1 : 64 / S;
+  const unsigned eblocks = 2u * (unsigned)((size_t)B / (size_t)gpw_min + (size_t)(n_keys < B ? n_keys : B) + 1);
+  hipLaunchKernelGGL(ipm_solve_elastic_sets_kernel, dim3(eblocks), dim3(64), 0, stream, e, (const double *)c->d_mqm_sets,
+                     (const Shared *)c->d_sets, n_keys);
+  HIPCHK(c, hipGetLastError());
+  return BTRAPZ_OK;
+}
+
+// The steps of a sets solve behind the entry points' refusals.  extended (btrapz_solve_long_sets_device): the warm long sets
+// kernel for candidates of 65..256 segments, and with opt->elastic == 1 the rescue pass -- every kernel choice is the one
+// btrapz_solve_long_rescue_device makes for a one-set batch of the same shape, options and start.
+static int solve_sets_steps(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index, const btrapz_options *opt,
+                            const btrapz_warm *warm, int B, int S, const double *seg, const int *seg_count, const double *init,
+                            const double *ref_end, const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters,
+                            void *stream_, bool extended) {
+  hipStream_t stream = (hipStream_t)stream_;
+  TRY(ws_open(c, stream));
+  c->last_launches = 1;   // (the sets solve never runs the two launches)
+  TRY(ensure_axis_ws(c, 2 * (size_t)B));
+  TRY(sets_tables(c, sets, n_sets, stream));
+  KernelArgs a;
+  fill_parameters(a, &sets[0], opt, warm);   // (a.sh is not read: every wavefront reads its own set)
+  batch_arguments(c, a, B, S, seg, init, ref_end, dl_bounds, ctrl, c->d_mqm_sets);
+  const bool warm_kernel = a.x0 || a.lam0 || a.lam_out;
+  const int elastic = (extended && opt) ? opt->elastic : 0;
+  const double *mq = c->d_mqm_sets; const Shared *dsets = c->d_sets;
+  // (ordered: a ragged batch always goes through the bucket list, a uniform one may take the split form; one launch:
+  //  cap_iter = -1, and blocks -- which only the automatic two launches look at -- is not known yet)
+  FormQuery q{};
+  q.B = B; q.S = S; q.ragged = seg_count != nullptr; q.warm_kernel = warm_kernel; q.ordered = seg_count != nullptr; q.compact = false;
+  q.elastic = 0; q.max_iter = a.max_iter; q.split = opt ? opt->split : 0; q.lean = opt ? opt->lean : 0; q.cap_iter = -1; q.queue = false;
+  q.unc_start = a.unc_start; q.resident_waves = c->resident_waves; q.blocks = 0;
+  const Form f = choose_form(q);
+  // (long form: the warm instantiation with a start or lam_out, and -- with a rescue pass -- beyond 192 segments whatever the
+  //  start, as solve_common picks it for btrapz_solve_long_rescue_device)
+  auto long_warm_kernel = [&](int segs) { return warm_kernel || (elastic && segs > BTRAPZ_MAX_SEGMENTS_LONG_RESCUE); };
+  if (f.long_form) {
+    c->last_form = long_warm_kernel(S) ? 16 : 2;
+    hipLaunchKernelGGL(long_warm_kernel(S) ? ipm_solve_long_warm_sets_kernel : ipm_solve_long_sets_kernel, dim3(2u * (unsigned)B),
+                       dim3(64u * (unsigned)((S + 63) / 64)), 0, stream, a, mq, dsets, set_index, n_sets);
+    HIPCHK(c, hipGetLastError());
+  } else if (f.split_on) {
+    c->last_form = 1;
+    hipLaunchKernelGGL(ipm_solve_sets_split_kernel, dim3(2u * (unsigned)B), dim3(64), 0, stream, a, mq, dsets, set_index, n_sets);
+    HIPCHK(c, hipGetLastError());
+  } else {
+    TRY(launch_sets_buckets(c, stream, a, seg_count, set_index, n_sets, f.lean_on, warm_kernel));
+  }
+  if (elastic) TRY(sets_rescue_pass(c, stream, a, seg_count, set_index, n_sets, f.long_form));
+  // Ragged batch with slots for more than 64 segments: its long candidates, each workgroup reading its candidate's set
+  // (btrapz_solve_sets_device: cold only -- warm starts keep them unsolved, as in solve_common; extended: warm-started too,
+  // and a count's plain launch followed by its rescue launch over the same list).
+  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && (!warm_kernel || extended)) {
+    auto launch = [&](const KernelArgs &l, unsigned n, int segs) {
+      hipLaunchKernelGGL(long_warm_kernel(segs) ? ipm_solve_long_warm_sets_kernel : ipm_solve_long_sets_kernel, dim3(2u * n),
+                         dim3(64u * (unsigned)((segs + 63) / 64)), 0, stream, l, mq, dsets, set_index, n_sets);
+      if (elastic) launch_long_rescue(c, stream, l, n, segs, set_index, n_sets);
+    };
+    TRY(solve_long_candidates(c, stream, a, seg_count, launch));
+  }
+  return finalize_and_close(c, stream, B, cost, status, iters);
+}
+
 BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
                                         const btrapz_options *opt, const btrapz_warm *warm, int B, int seg_stride,
                                         const double *seg, const int *seg_count, const double *init, const double *ref_end,
@@ -1279,44 +1392,44 @@ BTRAPZ_EXPORT int btrapz_solve_sets_device(btrapz_ctx *c, const btrapz_shared *s
     c->err = "invalid argument: with parameter sets, elastic, cap_iter > 0, compact = 1, queue and start are not served";
     return BTRAPZ_EINVAL;
   }
-  hipStream_t stream = (hipStream_t)stream_;
-  TRY(ws_open(c, stream));
-  c->last_launches = 1;   // (the sets solve never runs the two launches)
-  TRY(ensure_axis_ws(c, 2 * (size_t)B));
-  TRY(sets_tables(c, sets, n_sets, stream));
-  KernelArgs a;
-  fill_parameters(a, &sets[0], opt, warm);   // (a.sh is not read: every wavefront reads its own set)
-  batch_arguments(c, a, B, S, seg, init, ref_end, dl_bounds, ctrl, c->d_mqm_sets);
-  const bool warm_kernel = a.x0 || a.lam0 || a.lam_out;
-  const double *mq = c->d_mqm_sets; const Shared *dsets = c->d_sets;
-  // (ordered: a ragged batch always goes through the bucket list, a uniform one may take the split form; one launch:
-  //  cap_iter = -1, and blocks -- which only the automatic two launches look at -- is not known yet)
-  FormQuery q{};
-  q.B = B; q.S = S; q.ragged = seg_count != nullptr; q.warm_kernel = warm_kernel; q.ordered = seg_count != nullptr; q.compact = false;
-  q.elastic = 0; q.max_iter = a.max_iter; q.split = opt ? opt->split : 0; q.lean = opt ? opt->lean : 0; q.cap_iter = -1; q.queue = false;
-  q.unc_start = a.unc_start; q.resident_waves = c->resident_waves; q.blocks = 0;
-  const Form f = choose_form(q);
-  if (f.long_form) {
-    c->last_form = 2;
-    hipLaunchKernelGGL(ipm_solve_long_sets_kernel, dim3(2u * (unsigned)B), dim3(64u * (unsigned)((S + 63) / 64)), 0, stream, a,
-                       mq, dsets, set_index, n_sets);
-    HIPCHK(c, hipGetLastError());
-  } else if (f.split_on) {
-    c->last_form = 1;
-    hipLaunchKernelGGL(ipm_solve_sets_split_kernel, dim3(2u * (unsigned)B), dim3(64), 0, stream, a, mq, dsets, set_index, n_sets);
-    HIPCHK(c, hipGetLastError());
-  } else {
-    TRY(launch_sets_buckets(c, stream, a, seg_count, set_index, n_sets, f.lean_on, warm_kernel));
+  return solve_sets_steps(c, sets, n_sets, set_index, opt, warm, B, S, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
+                          iters, stream_, false);
+}
+
+// btrapz_solve_sets_device with warm starts and kept multipliers up to BTRAPZ_MAX_SEGMENTS_LONG segments and with the rescue
+// pass at every width (include/btrapz_hip_long_sets.h).  What the older call serves is handed to it; the rest is
+// solve_sets_steps, extended.
+BTRAPZ_EXPORT int btrapz_solve_long_sets_device(btrapz_ctx *c, const btrapz_shared *sets, int n_sets, const int *set_index,
+                                             const btrapz_options *opt, const btrapz_warm *warm, int B, int seg_stride,
+                                             const double *seg, const int *seg_count, const double *init, const double *ref_end,
+                                             const double *dl_bounds, double *ctrl, double *cost, int *status, int *iters,
+                                             void *stream) {
+  if (!c) return BTRAPZ_EINVAL;
+  const char *missing = !sets ? "sets" : !set_index ? "set_index" : !seg ? "seg" : !init ? "init" : !ref_end ? "ref_end" :
+                        !dl_bounds ? "dl_bounds" : !ctrl ? "ctrl" : !cost ? "cost" : !status ? "status" : nullptr;
+  const char *bad = missing ? nullptr : B < 1 ? "B < 1" : seg_stride < 1 ? "seg_stride < 1" :
+                    !sets_in_range(sets, n_sets) ? "n_sets outside 1..BTRAPZ_MAX_SETS" :
+                    seg_stride > BTRAPZ_MAX_SEGMENTS_LONG ? "seg_stride > BTRAPZ_MAX_SEGMENTS_LONG" : nullptr;
+  if (missing || bad) {
+    c->err = std::string("invalid argument: btrapz_solve_long_sets_device: ") + (missing ? std::string(missing) + " is NULL" : std::string(bad));
+    return BTRAPZ_EINVAL;
   }
-  // Cold ragged batch with slots for more than 64 segments: its long candidates, each workgroup reading its candidate's
-  // set (warm starts keep them unsolved, as in solve_common).
-  if (seg_count && S > BTRAPZ_MAX_SEGMENTS && !warm_kernel) {
-    auto launch = [&](const KernelArgs &l, unsigned n, int segs) {
-      hipLaunchKernelGGL(ipm_solve_long_sets_kernel, dim3(2u * n), dim3(64u * (unsigned)((segs + 63) / 64)), 0, stream, l, mq, dsets, set_index, n_sets);
-    };
-    TRY(solve_long_candidates(c, stream, a, seg_count, launch));
+  if (!options_ok(c, opt)) return BTRAPZ_EINVAL;
+  if (opt) {
+    const char *o = (opt->elastic < 0 || opt->elastic > 1) ? "btrapz_options.elastic: 0 or 1 (elastic rows for every candidate, 2, are not served with parameter sets)" :
+                    opt->cap_iter > 0 ? "btrapz_options.cap_iter > 0 is not served with parameter sets" :
+                    opt->compact > 0 ? "btrapz_options.compact = 1 is not served with parameter sets" :
+                    opt->queue > 0 ? "btrapz_options.queue is not served with parameter sets" :
+                    opt->start != 0 ? "btrapz_options.start is not served with parameter sets" : nullptr;
+    if (o) { c->err = std::string("invalid argument: ") + o; return BTRAPZ_EINVAL; }
   }
-  return finalize_and_close(c, stream, B, cost, status, iters);
+  if (!sets_alike(c, sets, n_sets)) return BTRAPZ_EINVAL;
+  const bool warm_args = warm && (warm->x0 || warm->lam0 || warm->lam_out);
+  if ((!opt || opt->elastic == 0) && (seg_stride <= BTRAPZ_MAX_SEGMENTS || !warm_args))
+    return btrapz_solve_sets_device(c, sets, n_sets, set_index, opt, warm, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds,
+                                    ctrl, cost, status, iters, stream);
+  return solve_sets_steps(c, sets, n_sets, set_index, opt, warm, B, seg_stride, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost,
+                          status, iters, stream, true);
 }
 
 // ---- gradients of a solve: btrapz_solve_vjp_device, btrapz_solve_jvp_device and their forms for 65..256 segments ----

@@ -99,11 +99,11 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
                                                const int *set_index = nullptr) {
   static_assert(!QUEUE || (!WARM && !ORDERED && !ELASTIC), "the queue serves uniform cold batches");
   static_assert(!SPLIT || (!ORDERED && !ELASTIC && !QUEUE), "the split form serves uniform batches");
-  static_assert(!MULTI || (!ORDERED && !QUEUE && !SPLIT && !(WARM && (ELASTIC || SETS))), "the long form serves uniform batches, cold (and their rescue pass) or warm-started -- and, launched once per segment count with a candidate list in a.order of a.bucket_S entries, the long candidates of a ragged batch");
+  static_assert(!MULTI || (!ORDERED && !QUEUE && !SPLIT && !(WARM && ELASTIC)), "the long form serves uniform batches, cold (and their rescue pass) or warm-started -- and, launched once per segment count with a candidate list in a.order of a.bucket_S entries, the long candidates of a ragged batch");
   static_assert(!(CAPPED || RESUME) || (!WARM && !ELASTIC && !QUEUE && !SPLIT && !MULTI && !(CAPPED && RESUME)), "capped / resume: packed cold form");
   static_assert(!RESUME || ORDERED, "the resume pass reads its problems from per-axis lists");
-  static_assert(!SETS || (!ELASTIC && !QUEUE && !CAPPED && !RESUME && (ORDERED ? !SPLIT && !MULTI : SPLIT || MULTI)),
-                "sets: ordered cold / warm forms, split and long form");
+  static_assert(!SETS || (!QUEUE && !CAPPED && !RESUME && !(WARM && ELASTIC) && (ORDERED ? !SPLIT && !MULTI : (SPLIT && !ELASTIC) || MULTI)),
+                "sets: ordered cold / warm forms and their rescue pass, split form, long form (cold, warm-started, rescue pass)");
   constexpr bool PERAXIS = ELASTIC || RESUME;   // one candidate list and one set of bucket tables per axis
   // value of the previous / next segment's lane (0 beyond the ends of the wavefront -- or, long form, of the workgroup)
   auto from_prev = [&](double x) -> double {
@@ -135,7 +135,22 @@ __device__ __forceinline__ void ipm_solve_body(const KernelArgs &a, const double
   const int axis = __builtin_amdgcn_readfirstlane(wave_id & 1);
   int S, pair = wave_id >> 1, ncand = a.B, cand0 = 0;
   [[maybe_unused]] int set = 0;
-  if constexpr (SETS && ORDERED) {
+  if constexpr (SETS && ORDERED && PERAXIS) {
+    // rescue pass of a sets batch: the stalled axis problems, bucketed per axis by the keys of the branch below -- one set
+    // of tables (3 n_keys + 2 entries: the layout of sets_prefix_kernel) and one candidate list per axis.  (A branch of
+    // its own: the plain sets instantiations below keep their instructions.)
+    const int *wave_prefix = a.wave_prefix + (size_t)axis * (3 * (size_t)n_keys + 2), *cand_prefix = a.cand_prefix + (size_t)axis * (3 * (size_t)n_keys + 2);
+    if (pair >= wave_prefix[n_keys]) return;
+    int s = 0, hi = n_keys;
+    while (hi - s > 1) {
+      const int mid = (s + hi) >> 1;
+      if (wave_prefix[mid] <= pair) s = mid; else hi = mid;
+    }
+    set = a.bucket_S ? s : s >> 6;
+    S = a.bucket_S ? a.bucket_S : 64 - (s & 63);
+    pair -= wave_prefix[s]; cand0 = cand_prefix[s] + axis * a.B; ncand = cand_prefix[s + 1] - cand_prefix[s];
+    set = __builtin_amdgcn_readfirstlane(set);
+  } else if constexpr (SETS && ORDERED) {
     // n_keys slots: key = set (uniform batch of a.bucket_S segments) or 64 set + 64 - segment count (ragged)
     if (pair >= a.wave_prefix[n_keys]) return;
     int s = 0, hi = n_keys;
@@ -1424,6 +1439,46 @@ __global__ __launch_bounds__(256) void ipm_solve_long_rescue_kernel(const Kernel
 __global__ __launch_bounds__(64) void ipm_solve_elastic_kernel(const KernelArgs a, const double *__restrict__ mqm) {
   __shared__ double lds[lds_rows<true>()][64];
   ipm_solve_body<false, true, true>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x);
+}
+// ---- btrapz_solve_long_sets_device: a parameter set per candidate beyond 64 segments with a warm start, and the rescue
+// pass of a sets batch at every width (SETS above).  Each is the one-set instantiation next to it with the set's scalars
+// and M'QM table read from sets[set] / mqm + 168 set.
+// Warm-started long form: the workgroup reads its candidate's set from set_index, as ipm_solve_long_sets_kernel does.
+__global__ __launch_bounds__(256) void ipm_solve_long_warm_sets_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                       const Shared *sets, const int *set_index, int n_sets) {
+  __shared__ double lds[4][lds_rows<false>()][64];
+  __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
+  const int wv = (int)threadIdx.x >> 6;
+  ipm_solve_body<true, false, false, false, false, true, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63,
+                                                                            wgs, wv, sets, n_sets, set_index);
+}
+// Rescue pass up to 64 segments: the stalled axis problems, listed per axis and bucketed by (set, segment count) -- the
+// tables of sets_prefix_kernel, one set of them per axis --, so that a wavefront holds one set.
+__global__ __launch_bounds__(64) void ipm_solve_elastic_sets_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                    const Shared *sets, int n_keys) {
+  __shared__ double lds[lds_rows<true>()][64];
+  ipm_solve_body<false, true, true, false, false, false, false, false, true>(a, mqm, lds, (int)blockIdx.x, (int)threadIdx.x,
+                                                                            nullptr, 0, sets, n_keys);
+}
+// Rescue pass of the long form, three wavefronts (65..192 segments) and four (193..256, without the reduction rows: see
+// ipm_solve_long_rescue_kernel).  A candidate whose set index is out of range did not stall: its workgroup leaves here.
+__global__ __launch_bounds__(192) void ipm_solve_long_elastic_sets_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                          const Shared *sets, const int *set_index, int n_sets) {
+  __shared__ double lds[3][lds_rows<true>()][64];
+  __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
+  if (!long_rescue_stalled(a)) return;
+  const int wv = (int)threadIdx.x >> 6;
+  ipm_solve_body<false, false, true, false, false, true, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63,
+                                                                            wgs, wv, sets, n_sets, set_index);
+}
+__global__ __launch_bounds__(256) void ipm_solve_long_rescue_sets_kernel(const KernelArgs a, const double *__restrict__ mqm,
+                                                                         const Shared *sets, const int *set_index, int n_sets) {
+  __shared__ double lds[4][4 * rows_kept<true>()][64];
+  __shared__ double wgs[WGS_SEAM + 4 * WGS_LANES];
+  if (!long_rescue_stalled(a)) return;
+  const int wv = (int)threadIdx.x >> 6;
+  ipm_solve_body<false, false, true, false, false, true, false, false, true>(a, mqm, lds[wv], (int)blockIdx.x, (int)threadIdx.x & 63,
+                                                                            wgs, wv, sets, n_sets, set_index);
 }
 // ---- candidates that cannot start (btrapz_options.compact) ------------------------------------------------------------
 // A quarter of the cuboid bench batch and of the knot-level pipeline's candidates end BEFORE the first iteration: an

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void sets_scatter_kernel(int B, int seg_stride
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const int key = i < B ? sets_key(i, seg_stride, seg_count, set_index, n_sets) : -1;
-  if (i < B && key < 0) {
+  if (i < B && key < 0 && axis_status) {   // (no records: the lists of the rescue pass, whose keyless problems have theirs)
     axis_obj[2 * (size_t)i] = 0.0; axis_obj[2 * (size_t)i + 1] = 0.0;
     axis_status[2 * (size_t)i] = BTRAPZ_NO_CORRIDOR; axis_status[2 * (size_t)i + 1] = BTRAPZ_NO_CORRIDOR;
     axis_iters[2 * (size_t)i] = 0; axis_iters[2 * (size_t)i + 1] = 0;
@@ -96,6 +96,18 @@ __global__ __launch_bounds__(256) void sets_scatter_kernel(int B, int seg_stride
     remaining &= ~m;
   }
   if (key >= 0) order[pos] = i;
+}
+
+// Rescue pass of a sets batch (btrapz_solve_long_sets_device): the three kernels above list the stalled problems of one
+// axis when they are given masked[axis] in place of set_index -- the candidate's set where that axis problem ended
+// BTRAPZ_MAX_ITER_REACHED, -1 (no key) elsewhere.  A candidate whose set index is out of range is BTRAPZ_NO_CORRIDOR
+// by then, not stalled.
+__global__ __launch_bounds__(256) void sets_rescue_index_kernel(int B, const int *set_index, const int *axis_status, int *masked) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int set = set_index[b];
+  masked[b] = axis_status[2 * (size_t)b] == BTRAPZ_MAX_ITER_REACHED ? set : -1;
+  masked[(size_t)B + b] = axis_status[2 * (size_t)b + 1] == BTRAPZ_MAX_ITER_REACHED ? set : -1;
 }
 
 }  // namespace btrapz

@@ -99,19 +99,22 @@ def solve(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, set_
     return _Solve.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, set_index, variant, delta)
 
 
-def _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta):
-    """_solve_kept through BatchSolver.solve_long: candidates of up to 256 segments, one parameter row (no sets)."""
+def _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta, set_index=None):
+    """_solve_kept through BatchSolver.solve_long: candidates of up to 256 segments; with set_index through
+    BatchSolver.solve_long_sets, a parameter row per set."""
     rec = DeviceBatch.from_tensors(*_on(solver, seg, init, ref_end, dl_bounds), seg_count=seg_count)
     sets = _sets_of_params(params, variant, delta)
     o = solver.new_result(rec.B, rec.S, zero_ctrl=True)
+    if set_index is not None:
+        return rec, sets, solver.solve_long_sets(rec, sets, set_index, keep_multipliers=True, out=o)
     return rec, sets, solver.solve_long(rec, sets[0], keep_multipliers=True, out=o)
 
 
 class _SolveLong(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, seg, init, ref_end, dl_bounds, params, solver, seg_count, variant, delta):
-        ctx.rec, ctx.sets, o = _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta)
-        ctx.solver, ctx.out = solver, o
+    def forward(ctx, seg, init, ref_end, dl_bounds, params, solver, seg_count, variant, delta, set_index):
+        ctx.rec, ctx.sets, o = _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta, set_index)
+        ctx.solver, ctx.set_index, ctx.out = solver, set_index, o
         ctx.params_shape, ctx.params_device = params.shape, params.device
         ctx.mark_non_differentiable(o["status"])
         return o["ctrl"], o["cost"], o["status"]
@@ -119,20 +122,31 @@ class _SolveLong(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ctrl_bar, cost_bar, _status_bar):
         if ctrl_bar is None and cost_bar is None:
-            return (None,) * 9
-        g = ctx.solver.solve_long_vjp(ctx.rec, ctx.sets, ctx.out, ctrl_bar, cost_bar)
+            return (None,) * 10
+        g = ctx.solver.solve_long_vjp(ctx.rec, ctx.sets, ctx.out, ctrl_bar, cost_bar, set_index=ctx.set_index)
         need = ctx.needs_input_grad
-        gp = _sum_rows(g["shared"], None, 1).reshape(ctx.params_shape).to(ctx.params_device) if need[4] else None
+        gp = _sum_rows(g["shared"], ctx.set_index, len(ctx.sets)).reshape(ctx.params_shape).to(ctx.params_device) if need[4] else None
         return (g["seg"] if need[0] else None, g["init"] if need[1] else None, g["ref_end"] if need[2] else None,
-                g["dl_bounds"] if need[3] else None, gp, None, None, None, None)
+                g["dl_bounds"] if need[3] else None, gp, None, None, None, None, None)
 
 
 def solve_long(solver, seg, init, ref_end, dl_bounds, params, *, seg_count=None, variant=0, delta=0.1):
     """diff.solve for candidates of up to 256 segments: the forward is BatchSolver.solve_long with the multipliers kept
     (btrapz_solve_long_warm_device, cold start, no rescue pass), the backward one btrapz_solve_long_vjp_device launch.
-    Arguments and results as diff.solve, with S up to 256 and params ONE row [20]: solve_long has no parameter sets."""
+    Arguments and results as diff.solve, with S up to 256 and params ONE row [20]; with a parameter row per set:
+    solve_long_sets."""
     _check_params(params, None)
-    return _SolveLong.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, variant, delta)
+    return _SolveLong.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, variant, delta, None)
+
+
+def solve_long_sets(solver, seg, init, ref_end, dl_bounds, params, *, set_index, seg_count=None, variant=0, delta=0.1):
+    """solve_long with a parameter set per candidate: params [n_sets, 20], set_index int32 [B].  The forward is
+    BatchSolver.solve_long_sets with the multipliers kept (btrapz_solve_long_sets_device, no rescue pass), the backward
+    btrapz_solve_long_vjp_device with set_index; the gradient rows of params are summed per set as diff.solve sums them."""
+    if set_index is None:
+        raise ValueError("solve_long_sets: set_index (int32 [B]) is required; one parameter row: solve_long")
+    _check_params(params, set_index)
+    return _SolveLong.apply(seg, init, ref_end, dl_bounds, params, solver, seg_count, variant, delta, set_index)
 
 
 class _TrajCost(torch.autograd.Function):
@@ -311,8 +325,22 @@ def solve_long_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, 
                         log=False, out=None):
     """diff.solve_jacobian for candidates of up to 256 segments: one BatchSolver.solve_long with the multipliers kept and
     ONE btrapz_solve_long_jvp_device call with T = len(columns) unit tangents on the named columns of the parameter row.
-    params: one row [20].  Arguments, `out` (with its precondition) and the returned dict as diff.solve_jacobian."""
-    _check_params(params, None)
+    params: one row [20] (a row per set: solve_long_sets_jacobian).  Arguments, `out` (with its precondition) and the returned
+    dict as diff.solve_jacobian."""
+    return _solve_long_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, seg_count, None, variant, delta, log, out)
+
+
+def solve_long_sets_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, *, set_index, seg_count=None, variant=0,
+                             delta=0.1, log=False, out=None):
+    """solve_long_jacobian with a parameter set per candidate: params [n_sets, 20], set_index int32 [B]; the solve is
+    BatchSolver.solve_long_sets with the multipliers kept, and each candidate's tangent sits on its own set's row."""
+    if set_index is None:
+        raise ValueError("solve_long_sets_jacobian: set_index (int32 [B]) is required; one parameter row: solve_long_jacobian")
+    return _solve_long_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, seg_count, set_index, variant, delta, log, out)
+
+
+def _solve_long_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, seg_count, set_index, variant, delta, log, out):
+    _check_params(params, set_index)
     if out is not None:
         B_, S_ = seg.shape[1], seg.shape[2]
         if out.get("lam") is None or tuple(out["ctrl"].shape) != (B_, 12 * S_) or tuple(out["lam"].shape) != (2, 36, B_, S_) \
@@ -323,15 +351,16 @@ def solve_long_jacobian(solver, seg, init, ref_end, dl_bounds, params, columns, 
         raise ValueError("columns: at least one, each in [0, %d)" % N_PARAMS)
     d = solver.device
     if out is None:
-        rec, sets, out = _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta)
+        rec, sets, out = _solve_long_kept(solver, seg, init, ref_end, dl_bounds, params, seg_count, variant, delta, set_index)
     else:
         rec = DeviceBatch.from_tensors(*_on(solver, seg, init, ref_end, dl_bounds), seg_count=seg_count)
         sets = _sets_of_params(params, variant, delta)
-    row = params.detach().to(d, torch.float64).reshape(N_PARAMS)
+    rows = params.detach().to(d, torch.float64).reshape(-1, N_PARAMS)
     tan = torch.zeros((len(columns), rec.B, N_PARAMS), dtype=torch.float64, device=d)
+    per_cand = rows[set_index.long().clamp(0, rows.shape[0] - 1)] if set_index is not None else rows[:1].expand(rec.B, N_PARAMS)
     for t, c in enumerate(columns):
-        tan[t, :, c] = row[c] if log else 1.0
-    j = solver.solve_long_jvp(rec, sets, out, {"shared": tan})
+        tan[t, :, c] = per_cand[:, c] if log else 1.0
+    j = solver.solve_long_jvp(rec, sets, out, {"shared": tan}, set_index=set_index)
     return dict(ctrl=out["ctrl"], cost=out["cost"], status=out["status"], dctrl=j["ctrl"], dcost=j["cost"], out=out)
 
 

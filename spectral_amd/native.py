@@ -275,6 +275,12 @@ PROTOTYPES_LONG_GRAD = {
                                           _vp]),
 }
 EXPORTS_LONG_GRAD = tuple(PROTOTYPES_LONG_GRAD)
+
+# Every function of include/btrapz_hip_long_sets.h, the same way (tests/test_long_sets_abi.py holds it to that header).
+PROTOTYPES_LONG_SETS = {
+    "btrapz_solve_long_sets_device": PROTOTYPES["btrapz_solve_sets_device"],
+}
+EXPORTS_LONG_SETS = tuple(PROTOTYPES_LONG_SETS)
 MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
 
 
@@ -355,7 +361,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()) + list(PROTOTYPES_LONG_SETS.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -577,6 +583,19 @@ class Context:
                                                    warm, B, seg_stride, _ptr(seg), _ptr(seg_count), _ptr(init),
                                                    _ptr(ref_end), _ptr(dl_bounds), _ptr(ctrl), _ptr(cost), _ptr(status),
                                                    _ptr(iters), _stream(stream)), "btrapz_solve_sets_device")
+
+    def solve_long_sets_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, cost, status,
+                               iters=None, x0=None, lam0=None, lam_out=None, mu0=0.0, smin=0.0, hint=None, stream=None,
+                               max_iter=0, eps=0.0, elastic=0, elastic_tol=0.0, cap_iter=0, lean=0, compact=0, split=0):
+        """btrapz_solve_long_sets_device (include/btrapz_hip_long_sets.h): solve_sets_device with warm starts and kept
+        multipliers up to 256 segments and with the rescue pass (elastic 0 or 1) at every width."""
+        opt = _options(max_iter, eps, elastic, elastic_tol, split=split, cap_iter=cap_iter, lean=lean, compact=compact)
+        use_warm = any(t is not None for t in (x0, lam0, lam_out, hint))
+        warm = C.byref(_warm(x0, lam0, lam_out, mu0, smin, hint)) if use_warm else None
+        self._check(lib().btrapz_solve_long_sets_device(self._h, _sets_array(sets), len(sets), _ptr(set_index), C.byref(opt),
+                                                        warm, B, seg_stride, _ptr(seg), _ptr(seg_count), _ptr(init),
+                                                        _ptr(ref_end), _ptr(dl_bounds), _ptr(ctrl), _ptr(cost), _ptr(status),
+                                                        _ptr(iters), _stream(stream)), "btrapz_solve_long_sets_device")
 
     def solve_vjp_device(self, B, seg_stride, sets, set_index, seg, seg_count, init, ref_end, dl_bounds, ctrl, lam, status,
                          ctrl_bar, cost_bar, g_seg=None, g_init=None, g_ref_end=None, g_dl_bounds=None, g_shared=None,

@@ -215,6 +215,22 @@ class BatchSolver:
         r = self._record(rec)
         return self._sets_call(r, sets, set_index, self.new_result(r.B, r.S, zero_ctrl=True), warm, keep_multipliers, options)
 
+    def solve_long_sets(self, dbatch_or_rec, sets, set_index, warm=None, keep_multipliers=False, out=None, elastic=0,
+                        elastic_tol=0.0, max_iter=0, eps=0.0, lean=0):
+        """solve_sets / solve_sets_ragged with what solve_long and solve_long_rescue give one set
+        (btrapz_solve_long_sets_device): candidates of up to 256 segments are warm-started from warm["x0"] / warm["lam"] and
+        return their multipliers as "lam", and with elastic = 1 a candidate of any width that stalls is solved again with
+        elastic rows under its own set (status 2 where its least violation is within elastic_tol).  Each candidate gets, bit
+        for bit, what solve_long_rescue gives it with its own set (lean pinned to 1 or -1).  A uniform batch, or a ragged
+        record whose stride may exceed 64; warm["hint"] is not read.  Returns the dict solve() returns."""
+        r = self._record(dbatch_or_rec)
+        _check_index(set_index, r.B)
+        w, o = self._warm(r, warm, keep_multipliers, self._out_of(r, out))
+        self.ctx.solve_long_sets_device(r.B, r.S, sets, set_index, r.seg, r.seg_count, r.init, r.ref_end, r.dl_bounds, o["ctrl"],
+                                        o["cost"], o["status"], o["iters"], stream=self._stream(), elastic=elastic,
+                                        elastic_tol=elastic_tol, max_iter=max_iter, eps=eps, lean=lean, **w)
+        return o
+
     def eval_states(self, dbatch, ctrl, times):
         """(p, v, a) of every candidate's solved trajectory at times[b][j] (seconds from the start of its
         horizon) -> [B, 2, n_times, 3]; the x0 of a warm start."""
