@@ -543,3 +543,59 @@ def trajectory_spread(solver, prisms, sigma, ds_bounds, dl_bounds_knots, s_ref, 
     status = jac["status"][sel]
     spread[(status != 1) & (status != 2)] = float("nan")
     return dict(traj=traj, npoints=npts, spread=spread, columns=columns, jac=jac)
+
+
+# ---- Cartesian states of Frenet trajectories (include/btrapz_hip_cartesian.h) -----------------------------------------
+
+class _Cartesian(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, frenet, refline, solver, layout, count, line_index):
+        f, = _on(solver, frenet)
+        ctx.solver, ctx.refline, ctx.layout, ctx.count, ctx.line_index, ctx.f = solver, refline, layout, count, line_index, f
+        ctx.shape, ctx.device_in = frenet.shape, frenet.device
+        return solver.cartesian(f, refline, layout=layout, count=count, line_index=line_index, want=("cart",))["cart"]
+
+    @staticmethod
+    def backward(ctx, cart_bar):
+        if cart_bar is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        g = ctx.solver.cartesian_vjp(ctx.f, ctx.refline, cart_bar, layout=ctx.layout, count=ctx.count, line_index=ctx.line_index)
+        return (g.reshape(ctx.shape).to(ctx.device_in), None, None, None, None, None)
+
+
+def cartesian(frenet, refline, solver, layout=0, count=None, line_index=None):
+    """Differentiable Cartesian states (btrapz_cartesian_device; backward: one btrapz_cartesian_vjp_device launch).
+    frenet: [R, 6, n] -- diff.sample's traj, layout 0 (BTRAPZ_FRENET_SAMPLES) -- or [R, 2, n, 3] -- diff.eval_states' x,
+    layout 1 (BTRAPZ_FRENET_STATES); refline: a layout.RefLine; count: int32 [R] (diff.sample's npoints), line_index: int32
+    [R].  Returns cart [R, 6, n], rows (x, y, theta, kappa, v, a); samples outside the line and beyond a row's count are
+    NaN and get a zero gradient -- reduce over the valid samples (torch.nansum, or a mask from count).  The interval of the
+    lookup is frozen and the reference line is not differentiated.  Composes with diff.sample / diff.eval_states /
+    diff.solve."""
+    return _Cartesian.apply(frenet, refline, solver, int(layout), count, line_index)
+
+
+def cartesian_jvp(solver, frenet, refline, frenet_dot, layout=0, count=None, line_index=None):
+    """Tangents of the Cartesian states (btrapz_cartesian_jvp_device): frenet as diff.cartesian, frenet_dot [T] x its
+    shape -- diff.sample_jvp's or diff.eval_states_jvp's result -> cart_dot [T, R, 6, n]."""
+    f, fd = _on(solver, frenet, frenet_dot)
+    return solver.cartesian_jvp(f, refline, fd, layout=int(layout), count=count, line_index=line_index)
+
+
+def scene_jacobian_cartesian(solver, refline, prisms, prisms_dot, ds_bounds, dl_bounds_knots, s_ref, l_ref, init, params, *, O,
+                             variant=0, delta=0.1, seg_stride=16, road=None, more=None, sel=None, line_index=None):
+    """Directional derivatives of the planned trajectories IN THE PLANE with respect to the scene: scene_jacobian, then
+    sample_jvp and cartesian_jvp on the sampled winners.  refline: a layout.RefLine; line_index: int32 [nsel]; sel: the
+    scenes to sample (int64, default every scene in order); the other arguments are scene_jacobian's.  Returns its dict
+    plus "traj" [nsel, 6, max_points] and "npoints" [nsel] (diff.sample's), "cart" [nsel, 6, max_points] and "dcart"
+    [T, nsel, 6, max_points]; a tangent set in `more["init"]` moves sample 0 too."""
+    jac = scene_jacobian(solver, prisms, prisms_dot, ds_bounds, dl_bounds_knots, s_ref, l_ref, init, params, O=O, variant=variant,
+                         delta=delta, seg_stride=seg_stride, road=road, more=more)
+    rec = jac["rec"]
+    d = solver.device
+    sel = (torch.arange(rec.B, device=d) if sel is None else sel.to(d)).to(torch.int64).contiguous()
+    traj, npts = solver.sample(rec, jac["ctrl"], sel, delta)
+    dinit = (more or {}).get("init")
+    dtraj = sample_jvp(solver, jac["dctrl"], rec.seg, dinit=dinit, seg_count=rec.seg_count, sel=sel, delta=delta)[..., :traj.shape[2]]
+    cart = solver.cartesian(traj, refline, count=npts, line_index=line_index, want=("cart",))["cart"]
+    dcart = cartesian_jvp(solver, traj, refline, dtraj, count=npts, line_index=line_index)
+    return dict(jac, traj=traj, npoints=npts, cart=cart, dcart=dcart)

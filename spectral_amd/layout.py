@@ -68,3 +68,48 @@ class Batch:
         """Bytes one solve must move: inputs + 12S control points + cost + status."""
         S = self.S
         return (NUM_SEG_FIELDS * S + 6 + 2 + 10) * 8 + 12 * S * 8 + 8 + 4
+
+
+REFLINE_FIELDS = ("rs", "rx", "ry", "rtheta", "rkappa", "rdkappa")
+
+
+class RefLine:
+    """The reference-line table of the Cartesian stage (btrapz_refline, include/btrapz_hip_cartesian.h): n_lines tables
+    of M >= 2 points each -- arc length rs (strictly increasing within a line), position rx, ry, heading rtheta,
+    curvature rkappa and its derivative rdkappa.  Each array is [M] (one line) or [n_lines, M], a host array or a
+    device tensor.  The constructor checks the shapes, M >= 2 and that rs increases (the device does not), on a host
+    copy it keeps as .host; .on(device) uploads once per device and hands the same six tensors out afterwards."""
+
+    def __init__(self, rs, rx, ry, rtheta, rkappa, rdkappa):
+        given = dict(zip(REFLINE_FIELDS, (rs, rx, ry, rtheta, rkappa, rdkappa)))
+        self._given = given
+        host = {}
+        for k, a in given.items():
+            a = a.detach().cpu().numpy() if hasattr(a, "detach") else a
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            host[k] = a[None, :] if a.ndim == 1 else a
+            if host[k].ndim != 2 or host[k].shape != host["rs"].shape:
+                raise ValueError("RefLine: %s has shape %s; every array is [M] or [n_lines, M] like rs %s"
+                                 % (k, a.shape, host["rs"].shape))
+        self.n_lines, self.M = host["rs"].shape
+        if self.n_lines < 1 or self.M < 2:
+            raise ValueError("RefLine: n_lines >= 1 and M >= 2 points per line, not %s" % (host["rs"].shape,))
+        if not bool((np.diff(host["rs"], axis=1) > 0).all()):
+            raise ValueError("RefLine: rs must be strictly increasing within every line")
+        self.host = host
+        self._device = {}
+
+    def on(self, device):
+        """The six arrays as contiguous float64 tensors [n_lines, M] on `device`, uploaded the first time."""
+        import torch
+        device = torch.device(device)
+        if device not in self._device:
+            out = []
+            for k in REFLINE_FIELDS:
+                a = self._given[k]
+                if torch.is_tensor(a) and a.device == device and a.dtype == torch.float64 and a.is_contiguous():
+                    out.append(a.detach().reshape(self.n_lines, self.M))
+                else:
+                    out.append(torch.from_numpy(self.host[k]).to(device))
+            self._device[device] = tuple(out)
+        return self._device[device]

@@ -281,6 +281,35 @@ PROTOTYPES_LONG_SETS = {
     "btrapz_solve_long_sets_device": PROTOTYPES["btrapz_solve_sets_device"],
 }
 EXPORTS_LONG_SETS = tuple(PROTOTYPES_LONG_SETS)
+
+
+class CRefLine(C.Structure):
+    """btrapz_refline (include/btrapz_hip_cartesian.h): n_lines tables of M points, device or host pointers."""
+    _fields_ = [("n_lines", C.c_int), ("M", C.c_int), ("rs", C.c_void_p), ("rx", C.c_void_p), ("ry", C.c_void_p),
+                ("rtheta", C.c_void_p), ("rkappa", C.c_void_p), ("rdkappa", C.c_void_p)]
+
+
+KIN_AUDIT = ("kappa_abs_max", "alat_abs_max", "a_min", "a_max", "v_max", "frame_min", "n_outside", "worst")
+
+
+class CKinAudit(C.Structure):
+    """btrapz_kin_audit (include/btrapz_hip_cartesian.h): the output pointers of the kinematic audit, in KIN_AUDIT's order."""
+    _fields_ = [(k, C.c_void_p) for k in KIN_AUDIT]
+
+
+FRENET_SAMPLES, FRENET_STATES = 0, 1   # BTRAPZ_FRENET_SAMPLES, BTRAPZ_FRENET_STATES
+_ref, _aud = C.POINTER(CRefLine), C.POINTER(CKinAudit)
+
+# Every function of include/btrapz_hip_cartesian.h, the same way (tests/test_abi_cartesian.py holds it to that header).
+PROTOTYPES_CARTESIAN = {
+    "btrapz_cartesian_device": (_i, [_vp, _ref, _vp, _i, _i, _i, _vp, _vp, _vp, _aud, _vp]),
+    "btrapz_cartesian_vjp_device": (_i, [_vp, _ref, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_cartesian_jvp_device": (_i, [_vp, _ref, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "btrapz_cartesian_host": (_i, [_ref, _vp, _i, _i, _i, _vp, _vp, _vp, _aud]),
+    "btrapz_cartesian_vjp_host": (_i, [_ref, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_cartesian_jvp_host": (_i, [_ref, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+}
+EXPORTS_CARTESIAN = tuple(PROTOTYPES_CARTESIAN)
 MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
 
 
@@ -361,7 +390,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()) + list(PROTOTYPES_LONG_SETS.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()) + list(PROTOTYPES_LONG_SETS.items()) + list(PROTOTYPES_CARTESIAN.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -832,6 +861,27 @@ class Context:
         self._check(lib().btrapz_gather_rows_device(self._h, int(n), _ptr(idx), int(index_base), int(B), int(row_doubles),
                                                     _ptr(src), _ptr(rows), _stream(stream)), "btrapz_gather_rows_device")
 
+    def cartesian_device(self, refline, line_index, R, n, layout, f, count, cart=None, audit=None, stream=None):
+        """btrapz_cartesian_device: refline = CRefLine of device pointers; f under `layout` (FRENET_SAMPLES [R, 6, n] /
+        FRENET_STATES [R, 2, n, 3]); line_index / count int32 [R] or None; cart [R, 6, n] and / or audit = dict name ->
+        device tensor (KIN_AUDIT; missing or None: not wanted) are overwritten."""
+        au = C.byref(CKinAudit(*[_ptr(audit.get(k)) for k in KIN_AUDIT])) if audit is not None else None
+        self._check(lib().btrapz_cartesian_device(self._h, C.byref(refline), _ptr(line_index), int(R), int(n), int(layout),
+                                                  _ptr(f), _ptr(count), _ptr(cart), au, _stream(stream)),
+                    "btrapz_cartesian_device")
+
+    def cartesian_vjp_device(self, refline, line_index, R, n, layout, f, count, cart_bar, f_bar, stream=None):
+        """btrapz_cartesian_vjp_device: f_bar (the layout of f) is overwritten."""
+        self._check(lib().btrapz_cartesian_vjp_device(self._h, C.byref(refline), _ptr(line_index), int(R), int(n), int(layout),
+                                                      _ptr(f), _ptr(count), _ptr(cart_bar), _ptr(f_bar), _stream(stream)),
+                    "btrapz_cartesian_vjp_device")
+
+    def cartesian_jvp_device(self, refline, line_index, R, n, layout, f, count, T, f_dot, cart_dot, stream=None):
+        """btrapz_cartesian_jvp_device: f_dot [T] x the layout of f; cart_dot [T, R, 6, n] is written at the samples read."""
+        self._check(lib().btrapz_cartesian_jvp_device(self._h, C.byref(refline), _ptr(line_index), int(R), int(n), int(layout),
+                                                      _ptr(f), _ptr(count), int(T), _ptr(f_dot), _ptr(cart_dot),
+                                                      _stream(stream)), "btrapz_cartesian_jvp_device")
+
     def sample_device(self, B, S, delta, seg, init, ctrl, sel, max_points, out, npoints, stream=None):
         self._check(lib().btrapz_sample_device(self._h, B, S, float(delta), _ptr(seg), _ptr(init), _ptr(ctrl),
                                                int(sel.numel()), _ptr(sel), int(max_points), _ptr(out), _ptr(npoints),
@@ -989,3 +1039,87 @@ def corridor_from_file(variant, input_path, cap=256):
     if n < 0:
         raise BtrapzError("btrapz_corridor_from_file(%s) -> %d" % (input_path, n))
     return [buf[i] for i in range(min(n, cap))]
+
+
+def _refline_host(refline):
+    """layout.RefLine -> (CRefLine of host pointers, the arrays it points into)."""
+    arrs = [refline.host[k] for k in L.REFLINE_FIELDS]
+    return CRefLine(refline.n_lines, refline.M, *[a.ctypes.data for a in arrs]), arrs
+
+
+def _frenet_host(f, layout):
+    """f as a contiguous float64 array under `layout` -> (f, R, n)."""
+    f = _np_f64(f)
+    if layout == FRENET_SAMPLES and f.ndim == 3 and f.shape[1] == 6:
+        return f, f.shape[0], f.shape[2]
+    if layout == FRENET_STATES and f.ndim == 4 and f.shape[1] == 2 and f.shape[3] == 3:
+        return f, f.shape[0], f.shape[2]
+    raise ValueError("f must be [R, 6, n] (FRENET_SAMPLES) or [R, 2, n, 3] (FRENET_STATES), not %s under layout %r" % (f.shape, layout))
+
+
+def _i32_host(a, R):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.shape != (R,):
+        raise ValueError("count / line_index must be [R]")
+    return a
+
+
+def cartesian_host(f, refline, layout=FRENET_SAMPLES, count=None, line_index=None, want=("cart", "audit"), cart=None):
+    """btrapz_cartesian_host(): the Cartesian stage on the host (no GPU).  f under `layout`; refline: a layout.RefLine.
+    Returns a dict: "cart" [R, 6, n] (rows x, y, theta, kappa, v, a; `cart`: the array to write into, so that a caller
+    sees what is left alone) and / or "audit", a dict of the KIN_AUDIT arrays."""
+    f, R, n = _frenet_host(f, layout)
+    t, keep = _refline_host(refline)
+    count, line_index = _i32_host(count, R), _i32_host(line_index, R)
+    out = {}
+    if "cart" in want:
+        out["cart"] = np.full((R, 6, n), np.nan) if cart is None else cart
+        assert out["cart"].dtype == np.float64 and out["cart"].flags.c_contiguous and out["cart"].shape == (R, 6, n)
+    au = None
+    if "audit" in want:
+        out["audit"] = {k: np.zeros(R) for k in KIN_AUDIT[:6]}
+        out["audit"]["n_outside"] = np.zeros(R, dtype=np.int32)
+        out["audit"]["worst"] = np.zeros((R, 6), dtype=np.int32)
+        au = C.byref(CKinAudit(*[_np_ptr(out["audit"][k]) for k in KIN_AUDIT]))
+    rc = lib().btrapz_cartesian_host(C.byref(t), _np_ptr(line_index), R, n, int(layout), _np_ptr(f), _np_ptr(count),
+                                     _np_ptr(out.get("cart")), au)
+    if rc != 0:
+        raise BtrapzError("btrapz_cartesian_host -> %d (invalid argument)" % rc)
+    return out
+
+
+def cartesian_vjp_host(f, refline, cart_bar, layout=FRENET_SAMPLES, count=None, line_index=None):
+    """btrapz_cartesian_vjp_host(): cart_bar [R, 6, n] -> f_bar, shaped like f."""
+    f, R, n = _frenet_host(f, layout)
+    t, keep = _refline_host(refline)
+    count, line_index = _i32_host(count, R), _i32_host(line_index, R)
+    cart_bar = _np_f64(cart_bar)
+    if cart_bar.shape != (R, 6, n):
+        raise ValueError("cart_bar must be [R, 6, n]")
+    f_bar = np.full(f.shape, np.nan)
+    rc = lib().btrapz_cartesian_vjp_host(C.byref(t), _np_ptr(line_index), R, n, int(layout), _np_ptr(f), _np_ptr(count),
+                                         _np_ptr(cart_bar), _np_ptr(f_bar))
+    if rc != 0:
+        raise BtrapzError("btrapz_cartesian_vjp_host -> %d (invalid argument)" % rc)
+    return f_bar
+
+
+def cartesian_jvp_host(f, refline, f_dot, layout=FRENET_SAMPLES, count=None, line_index=None, cart_dot=None):
+    """btrapz_cartesian_jvp_host(): f_dot [T] x the shape of f -> cart_dot [T, R, 6, n] (`cart_dot`: the array to write
+    into; samples at and beyond a row's count keep what it holds)."""
+    f, R, n = _frenet_host(f, layout)
+    t, keep = _refline_host(refline)
+    count, line_index = _i32_host(count, R), _i32_host(line_index, R)
+    f_dot = _np_f64(f_dot)
+    if f_dot.shape[1:] != f.shape:
+        raise ValueError("f_dot must be [T] x the shape of f")
+    T = f_dot.shape[0]
+    out = np.full((T, R, 6, n), np.nan) if cart_dot is None else cart_dot
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (T, R, 6, n)
+    rc = lib().btrapz_cartesian_jvp_host(C.byref(t), _np_ptr(line_index), R, n, int(layout), _np_ptr(f), _np_ptr(count), T,
+                                         _np_ptr(f_dot), _np_ptr(out))
+    if rc != 0:
+        raise BtrapzError("btrapz_cartesian_jvp_host -> %d (invalid argument)" % rc)
+    return out

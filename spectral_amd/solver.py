@@ -4,7 +4,7 @@ import numpy as np
 import torch
 
 from . import layout as L
-from .native import Context, CRoad
+from .native import Context, CRoad, CRefLine, FRENET_SAMPLES, FRENET_STATES, KIN_AUDIT, MAX_TANGENTS
 
 
 class DeviceBatch:
@@ -539,6 +539,86 @@ class BatchSolver:
         that cannot be audited come out False."""
         m, e = check["margin"], check["eq_res"]
         return (m >= -float(tol_rows)).reshape(m.shape[0], -1).all(dim=1) & (e <= float(tol_eq)).reshape(e.shape[0], -1).all(dim=1)
+
+    @staticmethod
+    def kinematic_admissible(audit, kappa_max, alat_max, a_lo, a_hi, frame_margin):
+        """A cartesian() audit (with "worst") -> [R] bool mask: |kappa| <= kappa_max, v^2 |kappa| <= alat_max,
+        a_lo <= a <= a_hi and 1 - kappa_r l >= frame_margin over the row's samples, no sample outside the reference line,
+        and every extreme attained by a sample (worst >= 0).  The last condition is what keeps out a row with nothing to
+        judge: a row without samples (count 0: an unsolved candidate), and a row whose samples all hold NaN -- such values
+        enter no extreme and are not counted in n_outside, so the row's extremes are the -inf / +inf of "nobody", which
+        every comparison above passes.  A row in which only SOME samples hold NaN is judged on the others: keep NaN out of
+        the Frenet samples (the sampler and eval_states write none for a solved candidate).  Mask cost with it before topk:
+        cost.masked_fill(~mask, inf)."""
+        return ((audit["kappa_abs_max"] <= float(kappa_max)) & (audit["alat_abs_max"] <= float(alat_max)) &
+                (audit["a_min"] >= float(a_lo)) & (audit["a_max"] <= float(a_hi)) &
+                (audit["frame_min"] >= float(frame_margin)) & (audit["n_outside"] == 0) & (audit["worst"] >= 0).all(dim=1))
+
+    # ---- Cartesian states, their kinematic audit and derivatives (include/btrapz_hip_cartesian.h) --
+    def _cartesian_args(self, frenet, refline, layout, count, line_index, detach=True):
+        f = self._f64(frenet, detach=detach)
+        if layout == FRENET_SAMPLES and f.dim() == 3 and f.shape[1] == 6:
+            R, n = f.shape[0], f.shape[2]
+        elif layout == FRENET_STATES and f.dim() == 4 and f.shape[1] == 2 and f.shape[3] == 3:
+            R, n = f.shape[0], f.shape[2]
+        else:
+            raise ValueError("frenet must be [R, 6, n] (FRENET_SAMPLES) or [R, 2, n, 3] (FRENET_STATES), not %s under layout %r"
+                             % (tuple(f.shape), layout))
+        for t in (count, line_index):
+            if t is not None:
+                _check_index(t, R)
+        arrays = refline.on(self.device)
+        t = CRefLine(refline.n_lines, refline.M, *[a.data_ptr() for a in arrays])
+        return f, R, n, t, arrays
+
+    def cartesian(self, frenet, refline, layout=FRENET_SAMPLES, count=None, line_index=None, want=("cart", "audit")):
+        """Frenet samples -> Cartesian states and / or their kinematic audit (btrapz_cartesian_device, one launch).
+        frenet: [R, 6, n] rows (s, ds, dds, l, dl, ddl) -- sample()'s out -- under FRENET_SAMPLES, or [R, 2, n, 3] --
+        eval_states()'s x -- under FRENET_STATES; refline: a layout.RefLine; count: int32 [R] (sample()'s npoints; None:
+        n samples per row); line_index: int32 [R] (None: line 0).  Returns a dict: "cart" [R, 6, n], rows (x, y, theta,
+        kappa, v, a), NaN at samples outside the line and beyond a row's count; "audit": a dict of "kappa_abs_max",
+        "alat_abs_max", "a_min", "a_max", "v_max", "frame_min" [R], "n_outside" [R] int32 and "worst" [R, 6] int32 (the
+        sample that attains each extreme, -1: none).  want=("audit",) reads the samples and writes 60 bytes per row."""
+        unknown = set(want) - {"cart", "audit"}
+        if unknown or not want:
+            raise ValueError("want: \"cart\" and / or \"audit\", not %r" % (want,))
+        f, R, n, t, keep = self._cartesian_args(frenet, refline, layout, count, line_index)
+        out = {}
+        if "cart" in want:
+            out["cart"] = torch.full((R, 6, n), float("nan"), dtype=torch.float64, device=self.device)
+        if "audit" in want:
+            out["audit"] = {k: self._empty(R) for k in KIN_AUDIT[:6]}
+            out["audit"]["n_outside"] = self._empty(R, dtype=torch.int32)
+            out["audit"]["worst"] = self._empty(R, 6, dtype=torch.int32)
+        self.ctx.cartesian_device(t, line_index, R, n, layout, f, count, out.get("cart"), out.get("audit"), stream=self._stream())
+        return out
+
+    def cartesian_vjp(self, frenet, refline, cart_bar, layout=FRENET_SAMPLES, count=None, line_index=None):
+        """Vector-Jacobian product of cartesian (btrapz_cartesian_vjp_device, one launch): cart_bar [R, 6, n] -> the
+        cotangent of frenet, in its shape (what sample_vjp / eval_states_vjp take); 0 at samples that are not read or lie
+        outside the line.  The interval of the lookup is frozen; the reference line gets no gradient."""
+        f, R, n, t, keep = self._cartesian_args(frenet, refline, layout, count, line_index)
+        cart_bar = self._f64(cart_bar, detach=True)
+        if tuple(cart_bar.shape) != (R, 6, n):
+            raise ValueError("cart_bar must be [R, 6, n] = %s, not %s" % ((R, 6, n), tuple(cart_bar.shape)))
+        f_bar = torch.empty_like(f)
+        self.ctx.cartesian_vjp_device(t, line_index, R, n, layout, f, count, cart_bar, f_bar, stream=self._stream())
+        return f_bar
+
+    def cartesian_jvp(self, frenet, refline, frenet_dot, layout=FRENET_SAMPLES, count=None, line_index=None):
+        """Forward-mode derivative of cartesian (btrapz_cartesian_jvp_device): frenet_dot [T] x the shape of frenet ->
+        cart_dot [T, R, 6, n], the per-sample Jacobian formed once per chunk of 32 directions; 0 at samples outside the line
+        and beyond a row's count."""
+        f, R, n, t, keep = self._cartesian_args(frenet, refline, layout, count, line_index)
+        fd = self._f64(frenet_dot, detach=True)
+        if fd.dim() != f.dim() + 1 or tuple(fd.shape[1:]) != tuple(f.shape):
+            raise ValueError("frenet_dot must be [T] x %s, not %s" % (tuple(f.shape), tuple(fd.shape)))
+        T = fd.shape[0]
+        out = self._zeros(T, R, 6, n)
+        for t0 in range(0, T, MAX_TANGENTS):
+            t1 = min(t0 + MAX_TANGENTS, T)
+            self.ctx.cartesian_jvp_device(t, line_index, R, n, layout, f, count, t1 - t0, fd[t0:t1], out[t0:t1], stream=self._stream())
+        return out
 
     def argmin(self, cost, group=None, index_base=0):
         """Arg-min of cost over contiguous groups (default: the whole batch). Device tensors."""

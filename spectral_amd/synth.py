@@ -234,3 +234,45 @@ def make_batch(B, S, config=2, variant=0, seed=None, dtype=np.float64, agents=No
     ref_end = np.stack([s_star[:, -1], l_star[:, -1]], axis=1).astype(dtype)
     dlb = np.tile(np.array([-2.0, 2.0] * 5, dtype=dtype), (B, 1))
     return Batch(B=B, S=S, seg=seg, init=init, ref_end=ref_end, dl_bounds=dlb), sh
+
+
+# ---- reference lines of the Cartesian stage (layout.RefLine), for tests and benchmarks ---------------------------------
+def _refline_s(length, h):
+    m = int(np.floor(length / h + 1e-9)) + 1
+    if m < 2:
+        raise ValueError("a reference line needs at least two points: length >= h")
+    return h * np.arange(m)
+
+
+def refline_straight(length, h, x0=0.0, y0=0.0, theta0=0.0):
+    """A straight line of `length` metres from (x0, y0) with heading theta0, a point every h metres."""
+    from .layout import RefLine
+    s = _refline_s(length, h)
+    z = np.zeros_like(s)
+    return RefLine(s, x0 + np.cos(theta0) * s, y0 + np.sin(theta0) * s, z + theta0, z, z)
+
+
+def refline_arc(length, h, radius, x0=0.0, y0=0.0, theta0=0.0):
+    """A circular arc of signed `radius` (positive: to the left): kappa = 1 / radius, theta = theta0 + s / radius."""
+    from .layout import RefLine
+    s = _refline_s(length, h)
+    k = 1.0 / radius
+    th = theta0 + k * s
+    return RefLine(s, x0 + (np.sin(th) - np.sin(theta0)) / k, y0 - (np.cos(th) - np.cos(theta0)) / k, th, np.full_like(s, k),
+                   np.zeros_like(s))
+
+
+def refline_clothoid(length, h, kappa0, dkappa, x0=0.0, y0=0.0, theta0=0.0):
+    """A clothoid: kappa = kappa0 + dkappa s, theta = theta0 + kappa0 s + dkappa s^2 / 2; x and y are the integrals of
+    cos theta and sin theta (Fresnel integrals), taken interval by interval with a 12-point Gauss-Legendre rule, which is
+    exact to rounding while the heading turns by less than a radian per interval."""
+    from .layout import RefLine
+    s = _refline_s(length, h)
+    theta = lambda u: theta0 + kappa0 * u + 0.5 * dkappa * u * u
+    g, w = np.polynomial.legendre.leggauss(12)
+    u = s[:-1, None] + 0.5 * h * (g[None, :] + 1.0)
+    dx = 0.5 * h * (np.cos(theta(u)) * w).sum(1)
+    dy = 0.5 * h * (np.sin(theta(u)) * w).sum(1)
+    x = x0 + np.concatenate([[0.0], np.cumsum(dx)])
+    y = y0 + np.concatenate([[0.0], np.cumsum(dy)])
+    return RefLine(s, x, y, theta(s), kappa0 + dkappa * s, np.full_like(s, dkappa))
