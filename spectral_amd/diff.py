@@ -599,3 +599,43 @@ def scene_jacobian_cartesian(solver, refline, prisms, prisms_dot, ds_bounds, dl_
     cart = solver.cartesian(traj, refline, count=npts, line_index=line_index, want=("cart",))["cart"]
     dcart = cartesian_jvp(solver, traj, refline, dtraj, count=npts, line_index=line_index)
     return dict(jac, traj=traj, npoints=npts, cart=cart, dcart=dcart)
+
+
+# ---- Cartesian states projected onto the reference line (include/btrapz_hip_frenet.h) ---------------------------------
+
+class _Frenet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cart, refline, solver, layout, order, count, line_index, s_window):
+        c, = _on(solver, cart)
+        o = solver.frenet(c, refline, layout=layout, order=order, count=count, line_index=line_index, s_window=s_window)
+        ctx.solver, ctx.refline, ctx.layout, ctx.order, ctx.count, ctx.line_index = solver, refline, layout, order, count, line_index
+        ctx.c, ctx.f, ctx.interval = c, o["frenet"], o["interval"]
+        ctx.shape, ctx.device_in = cart.shape, cart.device
+        ctx.mark_non_differentiable(o["interval"])
+        return o["frenet"], o["interval"]
+
+    @staticmethod
+    def backward(ctx, frenet_bar, _interval_bar):
+        if frenet_bar is None or not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        g = ctx.solver.frenet_vjp(ctx.c, ctx.refline, ctx.f, ctx.interval, frenet_bar, layout=ctx.layout, order=ctx.order,
+                                  count=ctx.count, line_index=ctx.line_index)
+        return (g.reshape(ctx.shape).to(ctx.device_in),) + (None,) * 7
+
+
+def frenet(cart, refline, solver, layout=0, order=2, count=None, line_index=None, s_window=None):
+    """Differentiable projection onto the reference line (btrapz_frenet_device; backward: one btrapz_frenet_vjp_device
+    launch).  cart: [R, 6, n], rows (x, y, theta, kappa, v, a) -- diff.cartesian's result, or measured poses; order 0, 1 or
+    2: the rows that are read and the derivatives that are returned; s_window: [R, 2] or None.  Returns (frenet, interval):
+    frenet [R, 6, n], rows (s, ds, dds, l, dl, ddl) under layout 0, or [R, 2, n, 3] under layout 1; interval [R, n] int32
+    (-1: OUTSIDE), not differentiable.  OUTSIDE samples and samples beyond a row's count are NaN and get a zero gradient.
+    The matched interval is frozen and the reference line is not differentiated; a query between two branches of the
+    line jumps where their distances tie."""
+    return _Frenet.apply(cart, refline, solver, int(layout), int(order), count, line_index, s_window)
+
+
+def frenet_jvp(solver, cart, refline, frenet, interval, cart_dot, layout=0, order=2, count=None, line_index=None):
+    """Tangents of the projection (btrapz_frenet_jvp_device): cart, frenet and interval as diff.frenet took and returned
+    them, cart_dot [T, R, 6, n] -> frenet_dot [T] x the shape of frenet."""
+    c, f, cd = _on(solver, cart, frenet, cart_dot)
+    return solver.frenet_jvp(c, refline, f, interval, cd, layout=int(layout), order=int(order), count=count, line_index=line_index)

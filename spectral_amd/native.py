@@ -310,6 +310,17 @@ PROTOTYPES_CARTESIAN = {
     "btrapz_cartesian_jvp_host": (_i, [_ref, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
 }
 EXPORTS_CARTESIAN = tuple(PROTOTYPES_CARTESIAN)
+
+# Every function of include/btrapz_hip_frenet.h, the same way (tests/test_abi_frenet.py holds it to that header).
+PROTOTYPES_FRENET = {
+    "btrapz_frenet_device": (_i, [_vp, _ref, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_frenet_vjp_device": (_i, [_vp, _ref, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_frenet_jvp_device": (_i, [_vp, _ref, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "btrapz_frenet_host": (_i, [_ref, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_frenet_vjp_host": (_i, [_ref, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_frenet_jvp_host": (_i, [_ref, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+}
+EXPORTS_FRENET = tuple(PROTOTYPES_FRENET)
 MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
 
 
@@ -390,7 +401,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()) + list(PROTOTYPES_LONG_SETS.items()) + list(PROTOTYPES_CARTESIAN.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()) + list(PROTOTYPES_LONG_SETS.items()) + list(PROTOTYPES_CARTESIAN.items()) + list(PROTOTYPES_FRENET.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -882,6 +893,28 @@ class Context:
                                                       _ptr(f), _ptr(count), int(T), _ptr(f_dot), _ptr(cart_dot),
                                                       _stream(stream)), "btrapz_cartesian_jvp_device")
 
+    def frenet_device(self, refline, line_index, R, n, layout, order, cart, count, s_window, frenet, interval=None,
+                      n_outside=None, stream=None):
+        """btrapz_frenet_device: cart [R, 6, n] -> frenet under `layout`; s_window [R, 2] or None; interval int32 [R, n] and
+        n_outside int32 [R] or None (not wanted)."""
+        self._check(lib().btrapz_frenet_device(self._h, C.byref(refline), _ptr(line_index), int(R), int(n), int(layout), int(order),
+                                               _ptr(cart), _ptr(count), _ptr(s_window), _ptr(frenet), _ptr(interval),
+                                               _ptr(n_outside), _stream(stream)), "btrapz_frenet_device")
+
+    def frenet_vjp_device(self, refline, line_index, R, n, layout, order, cart, frenet, interval, count, frenet_bar, cart_bar,
+                          stream=None):
+        """btrapz_frenet_vjp_device: cart_bar [R, 6, n] is overwritten."""
+        self._check(lib().btrapz_frenet_vjp_device(self._h, C.byref(refline), _ptr(line_index), int(R), int(n), int(layout),
+                                                   int(order), _ptr(cart), _ptr(frenet), _ptr(interval), _ptr(count),
+                                                   _ptr(frenet_bar), _ptr(cart_bar), _stream(stream)), "btrapz_frenet_vjp_device")
+
+    def frenet_jvp_device(self, refline, line_index, R, n, layout, order, cart, frenet, interval, count, T, cart_dot, frenet_dot,
+                          stream=None):
+        """btrapz_frenet_jvp_device: cart_dot [T, R, 6, n]; frenet_dot [T] x the layout of frenet is written at the samples read."""
+        self._check(lib().btrapz_frenet_jvp_device(self._h, C.byref(refline), _ptr(line_index), int(R), int(n), int(layout),
+                                                   int(order), _ptr(cart), _ptr(frenet), _ptr(interval), _ptr(count), int(T),
+                                                   _ptr(cart_dot), _ptr(frenet_dot), _stream(stream)), "btrapz_frenet_jvp_device")
+
     def sample_device(self, B, S, delta, seg, init, ctrl, sel, max_points, out, npoints, stream=None):
         self._check(lib().btrapz_sample_device(self._h, B, S, float(delta), _ptr(seg), _ptr(init), _ptr(ctrl),
                                                int(sel.numel()), _ptr(sel), int(max_points), _ptr(out), _ptr(npoints),
@@ -1122,4 +1155,89 @@ def cartesian_jvp_host(f, refline, f_dot, layout=FRENET_SAMPLES, count=None, lin
                                          _np_ptr(f_dot), _np_ptr(out))
     if rc != 0:
         raise BtrapzError("btrapz_cartesian_jvp_host -> %d (invalid argument)" % rc)
+    return out
+
+
+def _frenet_shape(layout, R, n):
+    return (R, 6, n) if layout == FRENET_SAMPLES else (R, 2, n, 3)
+
+
+def _cart_host(cart):
+    cart = _np_f64(cart)
+    if cart.ndim != 3 or cart.shape[1] != 6:
+        raise ValueError("cart must be [R, 6, n], not %s" % (cart.shape,))
+    return cart, cart.shape[0], cart.shape[2]
+
+
+def frenet_host(cart, refline, layout=FRENET_SAMPLES, order=2, count=None, line_index=None, s_window=None, frenet=None,
+                interval=None):
+    """btrapz_frenet_host(): the projection onto the reference line on the host (no GPU).  cart [R, 6, n] (rows x, y, theta,
+    kappa, v, a; rows above the order are not read); refline: a layout.RefLine; s_window [R, 2] or None.  Returns a dict:
+    "frenet" under `layout` (NaN at OUTSIDE samples), "interval" [R, n] int32 (-1: OUTSIDE), "n_outside" [R] int32.
+    `frenet` / `interval`: the arrays to write into, so that a caller sees what is left alone."""
+    if layout not in (FRENET_SAMPLES, FRENET_STATES):
+        raise ValueError("layout: FRENET_SAMPLES or FRENET_STATES, not %r" % (layout,))
+    cart, R, n = _cart_host(cart)
+    t, keep = _refline_host(refline)
+    count, line_index = _i32_host(count, R), _i32_host(line_index, R)
+    s_window = _np_f64(s_window)
+    if s_window is not None and s_window.shape != (R, 2):
+        raise ValueError("s_window must be [R, 2]")
+    out = dict(frenet=np.full(_frenet_shape(layout, R, n), np.nan) if frenet is None else frenet,
+               interval=np.full((R, n), -1, dtype=np.int32) if interval is None else interval,
+               n_outside=np.zeros(R, dtype=np.int32))
+    assert out["frenet"].dtype == np.float64 and out["frenet"].flags.c_contiguous and out["frenet"].shape == _frenet_shape(layout, R, n)
+    assert out["interval"].dtype == np.int32 and out["interval"].flags.c_contiguous and out["interval"].shape == (R, n)
+    rc = lib().btrapz_frenet_host(C.byref(t), _np_ptr(line_index), R, n, int(layout), int(order), _np_ptr(cart), _np_ptr(count),
+                                  _np_ptr(s_window), _np_ptr(out["frenet"]), _np_ptr(out["interval"]), _np_ptr(out["n_outside"]))
+    if rc != 0:
+        raise BtrapzError("btrapz_frenet_host -> %d (invalid argument)" % rc)
+    return out
+
+
+def _frenet_grad_host(cart, frenet, interval, layout):
+    cart, R, n = _cart_host(cart)
+    frenet = _np_f64(frenet)
+    if layout not in (FRENET_SAMPLES, FRENET_STATES) or frenet.shape != _frenet_shape(layout, R, n):
+        raise ValueError("frenet must be %s under layout %r, not %s" % (_frenet_shape(layout, R, n), layout, frenet.shape))
+    interval = np.ascontiguousarray(interval, dtype=np.int32)
+    if interval.shape != (R, n):
+        raise ValueError("interval must be [R, n]")
+    return cart, frenet, interval, R, n
+
+
+def frenet_vjp_host(cart, refline, frenet, interval, frenet_bar, layout=FRENET_SAMPLES, order=2, count=None, line_index=None):
+    """btrapz_frenet_vjp_host(): frenet_bar (shaped like frenet) -> cart_bar [R, 6, n]; cart, frenet and interval are the
+    forward's."""
+    cart, frenet, interval, R, n = _frenet_grad_host(cart, frenet, interval, layout)
+    t, keep = _refline_host(refline)
+    count, line_index = _i32_host(count, R), _i32_host(line_index, R)
+    frenet_bar = _np_f64(frenet_bar)
+    if frenet_bar.shape != frenet.shape:
+        raise ValueError("frenet_bar must be shaped like frenet")
+    cart_bar = np.full((R, 6, n), np.nan)
+    rc = lib().btrapz_frenet_vjp_host(C.byref(t), _np_ptr(line_index), R, n, int(layout), int(order), _np_ptr(cart), _np_ptr(frenet),
+                                      _np_ptr(interval), _np_ptr(count), _np_ptr(frenet_bar), _np_ptr(cart_bar))
+    if rc != 0:
+        raise BtrapzError("btrapz_frenet_vjp_host -> %d (invalid argument)" % rc)
+    return cart_bar
+
+
+def frenet_jvp_host(cart, refline, frenet, interval, cart_dot, layout=FRENET_SAMPLES, order=2, count=None, line_index=None,
+                    frenet_dot=None):
+    """btrapz_frenet_jvp_host(): cart_dot [T, R, 6, n] -> frenet_dot [T] x the shape of frenet (`frenet_dot`: the array to
+    write into; samples at and beyond a row's count keep what it holds)."""
+    cart, frenet, interval, R, n = _frenet_grad_host(cart, frenet, interval, layout)
+    t, keep = _refline_host(refline)
+    count, line_index = _i32_host(count, R), _i32_host(line_index, R)
+    cart_dot = _np_f64(cart_dot)
+    if cart_dot.ndim != 4 or cart_dot.shape[1:] != (R, 6, n):
+        raise ValueError("cart_dot must be [T, R, 6, n]")
+    T = cart_dot.shape[0]
+    out = np.full((T,) + frenet.shape, np.nan) if frenet_dot is None else frenet_dot
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (T,) + frenet.shape
+    rc = lib().btrapz_frenet_jvp_host(C.byref(t), _np_ptr(line_index), R, n, int(layout), int(order), _np_ptr(cart), _np_ptr(frenet),
+                                      _np_ptr(interval), _np_ptr(count), T, _np_ptr(cart_dot), _np_ptr(out))
+    if rc != 0:
+        raise BtrapzError("btrapz_frenet_jvp_host -> %d (invalid argument)" % rc)
     return out

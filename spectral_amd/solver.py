@@ -620,6 +620,106 @@ class BatchSolver:
             self.ctx.cartesian_jvp_device(t, line_index, R, n, layout, f, count, t1 - t0, fd[t0:t1], out[t0:t1], stream=self._stream())
         return out
 
+    # ---- Cartesian states projected onto the reference line (include/btrapz_hip_frenet.h) --------
+    def _frenet_args(self, cart, refline, layout, order, count, line_index):
+        c = self._f64(cart, detach=True)
+        if c.dim() != 3 or c.shape[1] != 6:
+            raise ValueError("cart must be [R, 6, n], not %s" % (tuple(c.shape),))
+        if layout not in (FRENET_SAMPLES, FRENET_STATES):
+            raise ValueError("layout: FRENET_SAMPLES or FRENET_STATES, not %r" % (layout,))
+        if order not in (0, 1, 2):
+            raise ValueError("order: 0, 1 or 2, not %r" % (order,))
+        R, n = c.shape[0], c.shape[2]
+        for t in (count, line_index):
+            if t is not None:
+                _check_index(t, R)
+        arrays = refline.on(self.device)
+        t = CRefLine(refline.n_lines, refline.M, *[a.data_ptr() for a in arrays])
+        shape = (R, 6, n) if layout == FRENET_SAMPLES else (R, 2, n, 3)
+        return c, R, n, t, arrays, shape
+
+    def frenet(self, cart, refline, layout=FRENET_SAMPLES, order=2, count=None, line_index=None, s_window=None):
+        """Cartesian states -> Frenet states on the reference line (btrapz_frenet_device, one launch): the inverse of
+        cartesian().  cart: [R, 6, n], rows (x, y, theta, kappa, v, a) -- cartesian()'s "cart"; rows above `order` (0: x, y;
+        1: also theta, v; 2: all) are not read.  refline: a layout.RefLine; count, line_index: int32 [R]; s_window: [R, 2]
+        (lo, hi) in arc length, the part of the line a row's queries are matched against (None: all of it).  Returns a
+        dict: "frenet" under `layout` ([R, 6, n] rows (s, ds, dds, l, dl, ddl), or [R, 2, n, 3]), NaN at samples OUTSIDE
+        the line and beyond a row's count, 0 above the order; "interval" [R, n] int32, the matched interval of the table
+        (-1: OUTSIDE or not read), which the derivatives take; "n_outside" [R] int32."""
+        c, R, n, t, keep, shape = self._frenet_args(cart, refline, layout, order, count, line_index)
+        win = self._f64(s_window, detach=True)
+        if win is not None and tuple(win.shape) != (R, 2):
+            raise ValueError("s_window must be [R, 2] = %s, not %s" % ((R, 2), tuple(win.shape)))
+        out = dict(frenet=torch.full(shape, float("nan"), dtype=torch.float64, device=self.device),
+                   interval=torch.full((R, n), -1, dtype=torch.int32, device=self.device),
+                   n_outside=self._empty(R, dtype=torch.int32))
+        self.ctx.frenet_device(t, line_index, R, n, layout, order, c, count, win, out["frenet"], out["interval"], out["n_outside"],
+                               stream=self._stream())
+        return out
+
+    def frenet_vjp(self, cart, refline, frenet, interval, frenet_bar, layout=FRENET_SAMPLES, order=2, count=None, line_index=None):
+        """Vector-Jacobian product of frenet (btrapz_frenet_vjp_device, one launch): frenet_bar, shaped like frenet -> the
+        cotangent of cart [R, 6, n]; 0 at samples that are not read or OUTSIDE.  cart, frenet and interval are the
+        forward's: nothing is searched again.  The interval is frozen; the reference line gets no gradient."""
+        c, R, n, t, keep, shape = self._frenet_args(cart, refline, layout, order, count, line_index)
+        f, fb = self._f64(frenet, detach=True), self._f64(frenet_bar, detach=True)
+        if tuple(f.shape) != shape or tuple(fb.shape) != shape:
+            raise ValueError("frenet and frenet_bar must be %s, not %s and %s" % (shape, tuple(f.shape), tuple(fb.shape)))
+        _check_index(interval, R * n)
+        cart_bar = self._empty(R, 6, n)
+        self.ctx.frenet_vjp_device(t, line_index, R, n, layout, order, c, f, interval, count, fb, cart_bar, stream=self._stream())
+        return cart_bar
+
+    def frenet_jvp(self, cart, refline, frenet, interval, cart_dot, layout=FRENET_SAMPLES, order=2, count=None, line_index=None):
+        """Forward-mode derivative of frenet (btrapz_frenet_jvp_device): cart_dot [T, R, 6, n] -> frenet_dot [T] x the shape
+        of frenet, the per-sample Jacobian formed once per chunk of 32 directions; 0 at OUTSIDE samples and beyond a row's
+        count."""
+        c, R, n, t, keep, shape = self._frenet_args(cart, refline, layout, order, count, line_index)
+        f, cd = self._f64(frenet, detach=True), self._f64(cart_dot, detach=True)
+        if tuple(f.shape) != shape:
+            raise ValueError("frenet must be %s, not %s" % (shape, tuple(f.shape)))
+        if cd.dim() != 4 or tuple(cd.shape[1:]) != (R, 6, n):
+            raise ValueError("cart_dot must be [T, R, 6, n] = [T, %d, 6, %d], not %s" % (R, n, tuple(cd.shape)))
+        _check_index(interval, R * n)
+        T = cd.shape[0]
+        out = self._zeros(T, *shape)
+        for t0 in range(0, T, MAX_TANGENTS):
+            t1 = min(t0 + MAX_TANGENTS, T)
+            self.ctx.frenet_jvp_device(t, line_index, R, n, layout, order, c, f, interval, count, t1 - t0, cd[t0:t1], out[t0:t1],
+                                       stream=self._stream())
+        return out
+
+    def init_from_cartesian(self, states, refline, line_index=None, s_window=None):
+        """Cartesian start states [B, 6] = (x, y, theta, kappa, v, a), one per candidate -> (init [B, 6] = (s, ds, dds, l,
+        dl, ddl), what a batch's `init` holds, and a [B] bool mask of the rows that are not OUTSIDE; an OUTSIDE row of
+        init is NaN).  One btrapz_frenet_device launch at order 2, written in the layout of init."""
+        st = self._f64(states, detach=True)
+        if st.dim() != 2 or st.shape[1] != 6:
+            raise ValueError("states must be [B, 6], not %s" % (tuple(st.shape),))
+        B = st.shape[0]
+        o = self.frenet(st.reshape(B, 6, 1), refline, layout=FRENET_STATES, order=2, line_index=line_index, s_window=s_window)
+        return o["frenet"].reshape(B, 6), o["interval"].reshape(B) >= 0
+
+    def prisms_from_cartesian(self, obstacles, refline, line_index=None, s_window=None):
+        """Obstacles in the plane [B, P, 8] = (x, y, t0, theta, v, T, active, reserved) -> (the prisms [B, P, 8] = (s0, l0,
+        t0, vel_s, vel_l, T, active, reserved) that prism_bounds takes, and n_outside [B] int64: the active obstacles of a
+        scene that are OUTSIDE the line; such an obstacle gets active = 0 and zeros for its four projected entries).  One
+        btrapz_frenet_device launch at order 1 (vel_s = ds, vel_l = dl); line_index, s_window: per scene."""
+        ob = self._f64(obstacles, detach=True)
+        if ob.dim() != 3 or ob.shape[2] != 8:
+            raise ValueError("obstacles must be [B, P, 8], not %s" % (tuple(ob.shape),))
+        B, P = ob.shape[0], ob.shape[1]
+        cart = self._zeros(B, 6, P)
+        cart[:, 0], cart[:, 1], cart[:, 2], cart[:, 4] = ob[:, :, 0], ob[:, :, 1], ob[:, :, 3], ob[:, :, 4]
+        o = self.frenet(cart, refline, order=1, line_index=line_index, s_window=s_window)
+        f, inside = o["frenet"], o["interval"] >= 0
+        active = ob[:, :, 6] != 0
+        zero = torch.zeros_like(f[:, 0])
+        pick = lambda row: torch.where(inside, f[:, row], zero)
+        prisms = torch.stack([pick(0), pick(3), ob[:, :, 2], pick(1), pick(4), ob[:, :, 5],
+                              torch.where(inside, ob[:, :, 6], zero), ob[:, :, 7]], dim=2).contiguous()
+        return prisms, (active & ~inside).sum(dim=1)
+
     def argmin(self, cost, group=None, index_base=0):
         """Arg-min of cost over contiguous groups (default: the whole batch). Device tensors."""
         B = cost.numel()
