@@ -1806,10 +1806,12 @@ BTRAPZ_EXPORT int btrapz_rescue_violations_device(btrapz_ctx *c, int B, double *
   if (B < 1 || !viol) { c->err = "invalid argument"; return BTRAPZ_EINVAL; }
   if ((size_t)B != c->viol_valid) { c->err = "the context's last solve of B candidates had no rescue pass (btrapz_options.elastic)"; return BTRAPZ_EINVAL; }
   hipStream_t stream = (hipStream_t)stream_;
-  TRY(ws_open(c, stream));   // (it reads the last solve's records and writes no workspace: nothing to close)
+  // It writes no workspace, but it READS the last solve's records: closed like every sequence, so that the next solve on
+  // another stream -- which clears and rewrites d_axis_viol -- waits for this read (ws_wait knows only the last closer).
+  TRY(ws_open(c, stream));
   hipLaunchKernelGGL(rescue_violations_kernel, dim3((4 * B + 255) / 256), dim3(256), 0, stream, B, (const double *)c->d_axis_viol, viol);
   HIPCHK(c, hipGetLastError());
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 BTRAPZ_EXPORT int btrapz_eval_states_device(btrapz_ctx *c, int B, int seg_stride, const int *seg_count, const double *seg,
@@ -1867,6 +1869,7 @@ static int launch_corridor_stage(btrapz_ctx *c, CorridorArgs a, bool prisms, hip
   // Two passes (corridor_kernels.hip): lists sized for the usual case first -- LDS per workgroup is what limits the
   // wavefronts per CU -- then the candidates that overflowed them, with the full capacities.
   GROW(c, d_retry, sizeof(int) * ((size_t)B + 1));
+  TRY(ws_wait(c, stream));   // (the retry counter and list are the context's: one launch sequence at a time)
   HIPCHK(c, hipMemsetAsync(c->d_retry, 0, sizeof(int), stream));
   a.retry_count = c->d_retry; a.retry_list = c->d_retry + 1;
   const int cap_o_big = 160 / num_obs, cap_sel_big = 64;        // MAX_ALL / O, MAX_SEL of corridor_kernels.hip
@@ -1914,7 +1917,7 @@ static int launch_corridor_stage(btrapz_ctx *c, CorridorArgs a, bool prisms, hip
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), lds_bytes(a.cap_o, a.cap_sel), stream, a, staged);
   }
   HIPCHK(c, hipGetLastError());
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 BTRAPZ_EXPORT int btrapz_corridor_batch_device(btrapz_ctx *c, int variant, int B, int N, int num_obs, double delta,
@@ -1972,6 +1975,7 @@ BTRAPZ_EXPORT int btrapz_corridor_batch_vjp_device(btrapz_ctx *c, int variant, i
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t stream = (hipStream_t)stream_;
   GROW(c, d_vjp_retry, sizeof(int) * ((size_t)B + 1));
+  TRY(ws_wait(c, stream));   // (as in launch_corridor_stage)
   HIPCHK(c, hipMemsetAsync(c->d_vjp_retry, 0, sizeof(int), stream));
   const size_t pairs = sizeof(double) * 2 * (size_t)B * num_obs * N, knots = sizeof(double) * (size_t)B * N;
   if (out->s_bounds) HIPCHK(c, hipMemsetAsync(out->s_bounds, 0, pairs, stream));
@@ -2003,7 +2007,7 @@ BTRAPZ_EXPORT int btrapz_corridor_batch_vjp_device(btrapz_ctx *c, int variant, i
     hipLaunchKernelGGL(corridor_vjp_kernel, dim3(blocks), dim3(64), corridor_vjp_lds(N, num_obs, a.cap_o, a.cap_sel, seg_stride, a.staged).bytes, stream, a);
     HIPCHK(c, hipGetLastError());
   }
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 // The forward-mode derivative of the stage (corridor_jvp.hip, include/btrapz_hip_stage_jvp.h): the backward pass's two
@@ -2039,6 +2043,7 @@ BTRAPZ_EXPORT int btrapz_corridor_batch_jvp_device(btrapz_ctx *c, int variant, i
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t stream = (hipStream_t)stream_;
   GROW(c, d_vjp_retry, sizeof(int) * ((size_t)B + 1));
+  TRY(ws_wait(c, stream));   // (as in launch_corridor_stage)
   HIPCHK(c, hipMemsetAsync(c->d_vjp_retry, 0, sizeof(int), stream));
   CorridorJvpArgs a;
   memset(&a, 0, sizeof a);
@@ -2065,7 +2070,7 @@ BTRAPZ_EXPORT int btrapz_corridor_batch_jvp_device(btrapz_ctx *c, int variant, i
     hipLaunchKernelGGL(corridor_jvp_kernel, dim3(blocks), dim3(64), corridor_vjp_lds(N, num_obs, a.cap_o, a.cap_sel, seg_stride, a.staged).bytes, stream, a);
     HIPCHK(c, hipGetLastError());
   }
-  return BTRAPZ_OK;
+  return ws_close(c, stream);
 }
 
 // Obstacle prisms -> strips -> corridors: btrapz_prism_bounds_device + btrapz_corridor_batch_device (num_obs = O) with
