@@ -639,3 +639,43 @@ def frenet_jvp(solver, cart, refline, frenet, interval, cart_dot, layout=0, orde
     them, cart_dot [T, R, 6, n] -> frenet_dot [T] x the shape of frenet."""
     c, f, cd = _on(solver, cart, frenet, cart_dot)
     return solver.frenet_jvp(c, refline, f, interval, cd, layout=int(layout), order=int(order), count=count, line_index=line_index)
+
+
+# ---- footprint clearance against moving obstacles (include/btrapz_hip_clearance.h) ------------------------------------
+
+class _Clearance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cart, obstacles, footprint, solver, scene_index, count):
+        c, = _on(solver, cart)
+        o = solver.clearance(c, obstacles, footprint, scene_index=scene_index, count=count, want=("clear", "which"))
+        ctx.solver, ctx.obstacles, ctx.footprint, ctx.scene_index, ctx.count = solver, obstacles, footprint, scene_index, count
+        ctx.c, ctx.which = c, o["which"]
+        ctx.shape, ctx.device_in = cart.shape, cart.device
+        ctx.mark_non_differentiable(o["which"])
+        return o["clear"], o["which"]
+
+    @staticmethod
+    def backward(ctx, clear_bar, _which_bar):
+        if clear_bar is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        g = ctx.solver.clearance_vjp(ctx.c, ctx.obstacles, ctx.footprint, ctx.which, clear_bar, scene_index=ctx.scene_index,
+                                     count=ctx.count)
+        return (g.reshape(ctx.shape).to(ctx.device_in),) + (None,) * 5
+
+
+def clearance(cart, obstacles, footprint, solver, scene_index=None, count=None):
+    """Differentiable clearance of the ego's rectangle against moving obstacles (btrapz_clearance_device; backward: one
+    btrapz_clearance_vjp_device launch).  cart: [R, 6, n] -- diff.cartesian's result; obstacles: a layout.Obstacles of the
+    same n; footprint: (half_length, half_width, centre_offset); scene_index, count: int32 [R].  Returns (clear, which):
+    clear [R, n] (NaN at invalid poses and beyond a row's count, +inf without an obstacle -- reduce over the finite ones),
+    which [R, n] int32, not differentiable.  The winning obstacle and feature are frozen (a one-sided derivative at a tie)
+    and the obstacles get no gradient.  Composes with diff.cartesian / diff.sample / diff.solve."""
+    return _Clearance.apply(cart, obstacles, footprint, solver, scene_index, count)
+
+
+def clearance_jvp(solver, cart, obstacles, footprint, which, cart_dot, obs_dot=None, scene_index=None, count=None):
+    """Tangents of the clearance (btrapz_clearance_jvp_device): cart and which as diff.clearance took and returned them,
+    cart_dot [T, R, 6, n] -- diff.cartesian_jvp's result -- and obs_dot [T, n_scenes, O, 3, n] or None -> clear_dot [T, R, n]."""
+    c, cd = _on(solver, cart, cart_dot)
+    od = _on(solver, obs_dot)[0] if obs_dot is not None else None
+    return solver.clearance_jvp(c, obstacles, footprint, which, cd, obs_dot=od, scene_index=scene_index, count=count)

@@ -73,6 +73,57 @@ class Batch:
 REFLINE_FIELDS = ("rs", "rx", "ry", "rtheta", "rkappa", "rdkappa")
 
 
+class Obstacles:
+    """The moving obstacles of the clearance stage (btrapz_obstacles, include/btrapz_hip_clearance.h): n_scenes scenes of up
+    to O rectangles at n samples.  pose: [O, 3, n] (one scene) or [n_scenes, O, 3, n], rows (x, y, theta), column j being
+    the obstacle at the time of sample j of the rows it is checked against (aligning the two is the caller's); a NaN in a
+    column means the obstacle is absent there.  half: [O, 2] or [n_scenes, O, 2], (half_length, half_width).  obs_count:
+    [n_scenes] or None (every scene has O).  Host arrays or device tensors.  The constructor checks the shapes and that
+    every half extent is > 0 and finite (the device does not), on a host copy it keeps as .host; .on(device) uploads once
+    per device and hands the same tensors out afterwards."""
+
+    def __init__(self, pose, half, obs_count=None):
+        self._given = dict(pose=pose, half=half, obs_count=obs_count)
+        to_host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else a
+        p = np.ascontiguousarray(to_host(pose), dtype=np.float64)
+        h = np.ascontiguousarray(to_host(half), dtype=np.float64)
+        if p.ndim == 3:
+            p = p[None]
+        if h.ndim == 2:
+            h = h[None]
+        if p.ndim != 4 or p.shape[2] != 3 or min(p.shape) < 1:
+            raise ValueError("Obstacles: pose is [O, 3, n] or [n_scenes, O, 3, n] with every extent >= 1, not %s" % (p.shape,))
+        self.n_scenes, self.O, _, self.n = p.shape
+        if h.shape != (self.n_scenes, self.O, 2):
+            raise ValueError("Obstacles: half is %s for this pose, not %s" % ((self.n_scenes, self.O, 2), h.shape))
+        if not bool((np.isfinite(h) & (h > 0)).all()):
+            raise ValueError("Obstacles: every half extent must be > 0 and finite")
+        c = None
+        if obs_count is not None:
+            c = np.ascontiguousarray(to_host(obs_count), dtype=np.int32)
+            if c.shape != (self.n_scenes,):
+                raise ValueError("Obstacles: obs_count is [n_scenes] = %s, not %s" % ((self.n_scenes,), c.shape))
+        self.host = dict(pose=p, half=h, obs_count=c)
+        self._device = {}
+
+    def on(self, device):
+        """(pose, half, obs_count or None) as contiguous tensors on `device`, uploaded the first time."""
+        import torch
+        device = torch.device(device)
+        if device not in self._device:
+            out = []
+            for k, dtype in (("pose", torch.float64), ("half", torch.float64), ("obs_count", torch.int32)):
+                a = self._given[k]
+                if a is None:
+                    out.append(None)
+                elif torch.is_tensor(a) and a.device == device and a.dtype == dtype and a.is_contiguous():
+                    out.append(a.detach().reshape(self.host[k].shape))
+                else:
+                    out.append(torch.from_numpy(self.host[k]).to(device))
+            self._device[device] = tuple(out)
+        return self._device[device]
+
+
 class RefLine:
     """The reference-line table of the Cartesian stage (btrapz_refline, include/btrapz_hip_cartesian.h): n_lines tables
     of M >= 2 points each -- arc length rs (strictly increasing within a line), position rx, ry, heading rtheta,

@@ -321,6 +321,42 @@ PROTOTYPES_FRENET = {
     "btrapz_frenet_jvp_host": (_i, [_ref, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 EXPORTS_FRENET = tuple(PROTOTYPES_FRENET)
+
+
+class CFootprint(C.Structure):
+    """btrapz_footprint (include/btrapz_hip_clearance.h): the ego's rectangle."""
+    _fields_ = [("half_length", C.c_double), ("half_width", C.c_double), ("centre_offset", C.c_double)]
+
+
+class CObstacles(C.Structure):
+    """btrapz_obstacles (include/btrapz_hip_clearance.h): n_scenes scenes of up to O obstacles at n samples, device or host
+    pointers."""
+    _fields_ = [("n_scenes", C.c_int), ("O", C.c_int), ("n", C.c_int), ("pose", C.c_void_p), ("half", C.c_void_p),
+                ("obs_count", C.c_void_p)]
+
+
+CLEAR_AUDIT = ("clear_min", "worst", "n_below", "n_invalid")
+
+
+class CClearAudit(C.Structure):
+    """btrapz_clear_audit (include/btrapz_hip_clearance.h): the output pointers of the clearance audit, in CLEAR_AUDIT's order."""
+    _fields_ = [(k, C.c_void_p) for k in CLEAR_AUDIT]
+
+
+CLEAR_FEATURES = 12         # BTRAPZ_CLEAR_FEATURES
+_d = C.c_double
+_foot, _obs, _caud = C.POINTER(CFootprint), C.POINTER(CObstacles), C.POINTER(CClearAudit)
+
+# Every function of include/btrapz_hip_clearance.h, the same way (tests/test_abi_clearance.py holds it to that header).
+PROTOTYPES_CLEARANCE = {
+    "btrapz_clearance_device": (_i, [_vp, _foot, _obs, _vp, _i, _i, _vp, _vp, _d, _vp, _vp, _caud, _vp]),
+    "btrapz_clearance_vjp_device": (_i, [_vp, _foot, _obs, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_clearance_jvp_device": (_i, [_vp, _foot, _obs, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "btrapz_clearance_host": (_i, [_foot, _obs, _vp, _i, _i, _vp, _vp, _d, _vp, _vp, _caud]),
+    "btrapz_clearance_vjp_host": (_i, [_foot, _obs, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "btrapz_clearance_jvp_host": (_i, [_foot, _obs, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+}
+EXPORTS_CLEARANCE = tuple(PROTOTYPES_CLEARANCE)
 MAX_TOPK = 64               # BTRAPZ_MAX_TOPK
 
 
@@ -401,7 +437,7 @@ def lib():
                               "(there is no CPU path)" % LIB_PATH)
         _bind_hip_runtime()
         l = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()) + list(PROTOTYPES_LONG_SETS.items()) + list(PROTOTYPES_CARTESIAN.items()) + list(PROTOTYPES_FRENET.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_STAGE_JVP.items()) + list(PROTOTYPES_SCHEDULE.items()) + list(PROTOTYPES_SELECT.items()) + list(PROTOTYPES_CHECK.items()) + list(PROTOTYPES_LONG.items()) + list(PROTOTYPES_LONG_RESCUE.items()) + list(PROTOTYPES_LONG_GRAD.items()) + list(PROTOTYPES_LONG_SETS.items()) + list(PROTOTYPES_CARTESIAN.items()) + list(PROTOTYPES_FRENET.items()) + list(PROTOTYPES_CLEARANCE.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = l
@@ -915,6 +951,31 @@ class Context:
                                                    int(order), _ptr(cart), _ptr(frenet), _ptr(interval), _ptr(count), int(T),
                                                    _ptr(cart_dot), _ptr(frenet_dot), _stream(stream)), "btrapz_frenet_jvp_device")
 
+    def clearance_device(self, footprint, obstacles, scene_index, R, n, cart, count, d_safe, clear=None, which=None, audit=None,
+                         stream=None):
+        """btrapz_clearance_device: footprint = CFootprint, obstacles = CObstacles of device pointers; cart [R, 6, n];
+        scene_index / count int32 [R] or None; clear [R, n], which int32 [R, n] and / or audit = dict name -> device tensor
+        (CLEAR_AUDIT; missing or None: not wanted) are overwritten at the samples read."""
+        au = C.byref(CClearAudit(*[_ptr(audit.get(k)) for k in CLEAR_AUDIT])) if audit is not None else None
+        self._check(lib().btrapz_clearance_device(self._h, C.byref(footprint), C.byref(obstacles), _ptr(scene_index), int(R), int(n),
+                                                  _ptr(cart), _ptr(count), float(d_safe), _ptr(clear), _ptr(which), au,
+                                                  _stream(stream)), "btrapz_clearance_device")
+
+    def clearance_vjp_device(self, footprint, obstacles, scene_index, R, n, cart, count, which, clear_bar, cart_bar, stream=None):
+        """btrapz_clearance_vjp_device: cart_bar [R, 6, n] is overwritten as a whole."""
+        self._check(lib().btrapz_clearance_vjp_device(self._h, C.byref(footprint), C.byref(obstacles), _ptr(scene_index), int(R),
+                                                      int(n), _ptr(cart), _ptr(count), _ptr(which), _ptr(clear_bar),
+                                                      _ptr(cart_bar), _stream(stream)), "btrapz_clearance_vjp_device")
+
+    def clearance_jvp_device(self, footprint, obstacles, scene_index, R, n, cart, count, which, T, cart_dot, obs_dot, clear_dot,
+                             stream=None):
+        """btrapz_clearance_jvp_device: cart_dot [T, R, 6, n], obs_dot [T, n_scenes, O, 3, n] or None; clear_dot [T, R, n] is
+        written at the samples read."""
+        self._check(lib().btrapz_clearance_jvp_device(self._h, C.byref(footprint), C.byref(obstacles), _ptr(scene_index), int(R),
+                                                      int(n), _ptr(cart), _ptr(count), _ptr(which), int(T), _ptr(cart_dot),
+                                                      _ptr(obs_dot), _ptr(clear_dot), _stream(stream)),
+                    "btrapz_clearance_jvp_device")
+
     def sample_device(self, B, S, delta, seg, init, ctrl, sel, max_points, out, npoints, stream=None):
         self._check(lib().btrapz_sample_device(self._h, B, S, float(delta), _ptr(seg), _ptr(init), _ptr(ctrl),
                                                int(sel.numel()), _ptr(sel), int(max_points), _ptr(out), _ptr(npoints),
@@ -1240,4 +1301,102 @@ def frenet_jvp_host(cart, refline, frenet, interval, cart_dot, layout=FRENET_SAM
                                       _np_ptr(interval), _np_ptr(count), T, _np_ptr(cart_dot), _np_ptr(out))
     if rc != 0:
         raise BtrapzError("btrapz_frenet_jvp_host -> %d (invalid argument)" % rc)
+    return out
+
+
+def footprint_struct(footprint):
+    """(half_length, half_width, centre_offset) or (half_length, half_width) -> CFootprint."""
+    if isinstance(footprint, CFootprint):
+        return footprint
+    f = tuple(float(v) for v in footprint)
+    if len(f) == 2:
+        f += (0.0,)
+    if len(f) != 3:
+        raise ValueError("footprint: (half_length, half_width[, centre_offset])")
+    return CFootprint(*f)
+
+
+def _obstacles_host(obstacles, n):
+    """layout.Obstacles -> (CObstacles of host pointers, the arrays it points into)."""
+    h = obstacles.host
+    keep = (h["pose"], h["half"], h["obs_count"])
+    return CObstacles(obstacles.n_scenes, obstacles.O, obstacles.n, h["pose"].ctypes.data, h["half"].ctypes.data,
+                      h["obs_count"].ctypes.data if h["obs_count"] is not None else None), keep
+
+
+def _which_host(which, R, n):
+    which = np.ascontiguousarray(which, dtype=np.int32)
+    if which.shape != (R, n):
+        raise ValueError("which must be [R, n]")
+    return which
+
+
+def clearance_host(cart, obstacles, footprint, scene_index=None, count=None, d_safe=0.0, want=("clear", "which", "audit"),
+                   clear=None, which=None):
+    """btrapz_clearance_host(): the clearance stage on the host (no GPU).  cart [R, 6, n]; obstacles: a layout.Obstacles;
+    footprint: (half_length, half_width, centre_offset).  Returns a dict: "clear" [R, n], "which" [R, n] int32 (`clear` /
+    `which`: the arrays to write into, so that a caller sees what is left alone) and / or "audit", a dict of the
+    CLEAR_AUDIT arrays."""
+    cart, R, n = _cart_host(cart)
+    ft = footprint_struct(footprint)
+    ob, keep = _obstacles_host(obstacles, n)
+    count, scene_index = _i32_host(count, R), _i32_host(scene_index, R)
+    out = {}
+    if "clear" in want:
+        out["clear"] = np.full((R, n), np.nan) if clear is None else clear
+        assert out["clear"].dtype == np.float64 and out["clear"].flags.c_contiguous and out["clear"].shape == (R, n)
+    if "which" in want:
+        out["which"] = np.full((R, n), -1, dtype=np.int32) if which is None else which
+        assert out["which"].dtype == np.int32 and out["which"].flags.c_contiguous and out["which"].shape == (R, n)
+    au = None
+    if "audit" in want:
+        out["audit"] = dict(clear_min=np.zeros(R), worst=np.zeros((R, 2), dtype=np.int32), n_below=np.zeros(R, dtype=np.int32),
+                            n_invalid=np.zeros(R, dtype=np.int32))
+        au = C.byref(CClearAudit(*[_np_ptr(out["audit"][k]) for k in CLEAR_AUDIT]))
+    rc = lib().btrapz_clearance_host(C.byref(ft), C.byref(ob), _np_ptr(scene_index), R, n, _np_ptr(cart), _np_ptr(count),
+                                     float(d_safe), _np_ptr(out.get("clear")), _np_ptr(out.get("which")), au)
+    if rc != 0:
+        raise BtrapzError("btrapz_clearance_host -> %d (invalid argument)" % rc)
+    return out
+
+
+def clearance_vjp_host(cart, obstacles, footprint, which, clear_bar, scene_index=None, count=None):
+    """btrapz_clearance_vjp_host(): clear_bar [R, n] -> cart_bar [R, 6, n] under the forward's `which`."""
+    cart, R, n = _cart_host(cart)
+    ft = footprint_struct(footprint)
+    ob, keep = _obstacles_host(obstacles, n)
+    count, scene_index = _i32_host(count, R), _i32_host(scene_index, R)
+    which = _which_host(which, R, n)
+    clear_bar = _np_f64(clear_bar)
+    if clear_bar.shape != (R, n):
+        raise ValueError("clear_bar must be [R, n]")
+    cart_bar = np.full((R, 6, n), np.nan)
+    rc = lib().btrapz_clearance_vjp_host(C.byref(ft), C.byref(ob), _np_ptr(scene_index), R, n, _np_ptr(cart), _np_ptr(count),
+                                         _np_ptr(which), _np_ptr(clear_bar), _np_ptr(cart_bar))
+    if rc != 0:
+        raise BtrapzError("btrapz_clearance_vjp_host -> %d (invalid argument)" % rc)
+    return cart_bar
+
+
+def clearance_jvp_host(cart, obstacles, footprint, which, cart_dot, obs_dot=None, scene_index=None, count=None, clear_dot=None):
+    """btrapz_clearance_jvp_host(): cart_dot [T, R, 6, n] and obs_dot [T, n_scenes, O, 3, n] or None -> clear_dot [T, R, n]
+    (`clear_dot`: the array to write into; samples at and beyond a row's count keep what it holds)."""
+    cart, R, n = _cart_host(cart)
+    ft = footprint_struct(footprint)
+    ob, keep = _obstacles_host(obstacles, n)
+    count, scene_index = _i32_host(count, R), _i32_host(scene_index, R)
+    which = _which_host(which, R, n)
+    cart_dot = _np_f64(cart_dot)
+    if cart_dot.ndim != 4 or cart_dot.shape[1:] != (R, 6, n):
+        raise ValueError("cart_dot must be [T, R, 6, n]")
+    T = cart_dot.shape[0]
+    obs_dot = _np_f64(obs_dot)
+    if obs_dot is not None and obs_dot.shape != (T, obstacles.n_scenes, obstacles.O, 3, n):
+        raise ValueError("obs_dot must be [T, n_scenes, O, 3, n]")
+    out = np.full((T, R, n), np.nan) if clear_dot is None else clear_dot
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (T, R, n)
+    rc = lib().btrapz_clearance_jvp_host(C.byref(ft), C.byref(ob), _np_ptr(scene_index), R, n, _np_ptr(cart), _np_ptr(count),
+                                         _np_ptr(which), T, _np_ptr(cart_dot), _np_ptr(obs_dot), _np_ptr(out))
+    if rc != 0:
+        raise BtrapzError("btrapz_clearance_jvp_host -> %d (invalid argument)" % rc)
     return out

@@ -4,7 +4,8 @@ import numpy as np
 import torch
 
 from . import layout as L
-from .native import Context, CRoad, CRefLine, FRENET_SAMPLES, FRENET_STATES, KIN_AUDIT, MAX_TANGENTS
+from .native import (Context, CObstacles, CRoad, CRefLine, FRENET_SAMPLES, FRENET_STATES, KIN_AUDIT, MAX_TANGENTS,
+                     footprint_struct)
 
 
 class DeviceBatch:
@@ -618,6 +619,92 @@ class BatchSolver:
         for t0 in range(0, T, MAX_TANGENTS):
             t1 = min(t0 + MAX_TANGENTS, T)
             self.ctx.cartesian_jvp_device(t, line_index, R, n, layout, f, count, t1 - t0, fd[t0:t1], out[t0:t1], stream=self._stream())
+        return out
+
+    # ---- footprint clearance against moving obstacles (include/btrapz_hip_clearance.h) -----------
+    @staticmethod
+    def collision_free(audit, d_safe):
+        """A clearance() audit -> [R] bool mask: the row's smallest clearance is >= d_safe and no sample read had an invalid
+        pose -- written as comparisons that a NaN fails.  A row with nothing to judge (count 0: an unsolved candidate, or
+        no obstacle present anywhere) has clear_min = +inf and PASSES this mask: combine it with kinematic_admissible,
+        which keeps a row without samples out, and mask cost with both before topk:
+        cost.masked_fill(~(kin & free), inf)."""
+        return (audit["clear_min"] >= float(d_safe)) & (audit["n_invalid"] == 0)
+
+    def _clearance_args(self, cart, obstacles, footprint, scene_index, count):
+        c = self._f64(cart, detach=True)
+        if c.dim() != 3 or c.shape[1] != 6:
+            raise ValueError("cart must be [R, 6, n], not %s" % (tuple(c.shape),))
+        R, n = c.shape[0], c.shape[2]
+        if obstacles.n != n:
+            raise ValueError("obstacles hold %d samples, cart %d" % (obstacles.n, n))
+        for t in (count, scene_index):
+            if t is not None:
+                _check_index(t, R)
+        arrays = obstacles.on(self.device)
+        ob = CObstacles(obstacles.n_scenes, obstacles.O, obstacles.n, arrays[0].data_ptr(), arrays[1].data_ptr(),
+                        arrays[2].data_ptr() if arrays[2] is not None else None)
+        return c, R, n, footprint_struct(footprint), ob, arrays
+
+    def clearance(self, cart, obstacles, footprint, scene_index=None, count=None, d_safe=0.0, want=("clear", "which", "audit")):
+        """The signed clearance of the ego's rectangle against the scene's obstacle rectangles at every sample, and / or its
+        audit per row (btrapz_clearance_device: one kernel launch, behind the two fills that give "clear" and "which" their
+        NaN / -1 beyond a row's count).  cart: [R, 6, n] -- cartesian()'s "cart" (rows x, y, theta are
+        read); obstacles: a layout.Obstacles with the same n; footprint: (half_length, half_width, centre_offset);
+        scene_index: int32 [R] (None: scene 0); count: int32 [R] (None: n samples per row).  Returns a dict: "clear" [R, n]
+        (< 0: minus the penetration depth; NaN: invalid pose or beyond the count; +inf: no obstacle), "which" [R, n] int32
+        (obstacle * 16 + feature, -1: none), "audit": "clear_min" [R], "worst" [R, 2] int32 (sample, obstacle), "n_below"
+        [R] int32 (samples with clearance < d_safe), "n_invalid" [R] int32."""
+        unknown = set(want) - {"clear", "which", "audit"}
+        if unknown or not want:
+            raise ValueError("want: \"clear\", \"which\" and / or \"audit\", not %r" % (want,))
+        c, R, n, ft, ob, keep = self._clearance_args(cart, obstacles, footprint, scene_index, count)
+        out = {}
+        if "clear" in want:
+            out["clear"] = torch.full((R, n), float("nan"), dtype=torch.float64, device=self.device)
+        if "which" in want:
+            out["which"] = torch.full((R, n), -1, dtype=torch.int32, device=self.device)
+        if "audit" in want:
+            out["audit"] = dict(clear_min=self._empty(R), worst=self._empty(R, 2, dtype=torch.int32),
+                                n_below=self._empty(R, dtype=torch.int32), n_invalid=self._empty(R, dtype=torch.int32))
+        self.ctx.clearance_device(ft, ob, scene_index, R, n, c, count, d_safe, out.get("clear"), out.get("which"), out.get("audit"),
+                                  stream=self._stream())
+        return out
+
+    def clearance_vjp(self, cart, obstacles, footprint, which, clear_bar, scene_index=None, count=None):
+        """Vector-Jacobian product of clearance under the forward's `which` (btrapz_clearance_vjp_device, one launch):
+        clear_bar [R, n] -> cart_bar [R, 6, n] (what cartesian_vjp takes); rows kappa, v, a and every sample that is not
+        read, invalid or without an obstacle are 0.  The obstacles get no gradient in reverse mode."""
+        c, R, n, ft, ob, keep = self._clearance_args(cart, obstacles, footprint, scene_index, count)
+        cb = self._f64(clear_bar, detach=True)
+        if tuple(cb.shape) != (R, n) or tuple(which.shape) != (R, n):
+            raise ValueError("clear_bar and which must be [R, n] = %s" % ((R, n),))
+        _check_index(which, R * n)
+        cart_bar = torch.empty_like(c)
+        self.ctx.clearance_vjp_device(ft, ob, scene_index, R, n, c, count, which, cb, cart_bar, stream=self._stream())
+        return cart_bar
+
+    def clearance_jvp(self, cart, obstacles, footprint, which, cart_dot, obs_dot=None, scene_index=None, count=None):
+        """Forward-mode derivative of clearance under the forward's `which` (btrapz_clearance_jvp_device, one launch per 32
+        tangents behind a zero fill of the result): cart_dot
+        [T, R, 6, n] and obs_dot [T, n_scenes, O, 3, n] (None: the obstacles do not move) -> clear_dot [T, R, n]; 0 at
+        samples beyond a row's count, with an invalid pose or without an obstacle."""
+        c, R, n, ft, ob, keep = self._clearance_args(cart, obstacles, footprint, scene_index, count)
+        cd = self._f64(cart_dot, detach=True)
+        if cd.dim() != 4 or tuple(cd.shape[1:]) != (R, 6, n):
+            raise ValueError("cart_dot must be [T, R, 6, n], not %s" % (tuple(cd.shape),))
+        T = cd.shape[0]
+        od = self._f64(obs_dot, detach=True)
+        if od is not None and tuple(od.shape) != (T, obstacles.n_scenes, obstacles.O, 3, n):
+            raise ValueError("obs_dot must be [T, n_scenes, O, 3, n]")
+        if tuple(which.shape) != (R, n):
+            raise ValueError("which must be [R, n]")
+        _check_index(which, R * n)
+        out = self._zeros(T, R, n)
+        for t0 in range(0, T, MAX_TANGENTS):
+            t1 = min(t0 + MAX_TANGENTS, T)
+            self.ctx.clearance_jvp_device(ft, ob, scene_index, R, n, c, count, which, t1 - t0, cd[t0:t1],
+                                          od[t0:t1] if od is not None else None, out[t0:t1], stream=self._stream())
         return out
 
     # ---- Cartesian states projected onto the reference line (include/btrapz_hip_frenet.h) --------

@@ -276,3 +276,28 @@ def refline_clothoid(length, h, kappa0, dkappa, x0=0.0, y0=0.0, theta0=0.0):
     x = x0 + np.concatenate([[0.0], np.cumsum(dx)])
     y = y0 + np.concatenate([[0.0], np.cumsum(dy)])
     return RefLine(s, x, y, theta(s), kappa0 + dkappa * s, np.full_like(s, dkappa))
+
+
+# ---- moving obstacles of the clearance stage (layout.Obstacles), for tests and benchmarks ------------------------------
+def obstacles_on_line(refline, s0, l0, v, n, dt, half=(2.4, 1.0), dtheta=0.0, obs_count=None, line_index=0):
+    """Obstacles that keep their lateral offset and speed along a reference line: obstacle o of scene k starts at arc
+    length s0[k, o] with offset l0[k, o] and moves at v[k, o] m/s; sample j is the time j dt.  s0, l0, v: [O] (one scene) or
+    [n_scenes, O]; half: (half_length, half_width) for all, or [n_scenes, O, 2]; dtheta: added to the heading of the path
+    (scalar or like s0); line_index: the line of the table they move on.  The poses come from the Cartesian stage's host
+    twin (native.cartesian_host), so an obstacle that runs off the table is NaN from there on: absent.  Returns a
+    layout.Obstacles."""
+    from . import native
+    from .layout import Obstacles
+    s0, l0, v = np.broadcast_arrays(*[np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (s0, l0, v)])
+    K, O = s0.shape
+    t = dt * np.arange(int(n))
+    f = np.zeros((K * O, 6, int(n)))
+    f[:, 0] = s0.reshape(-1, 1) + v.reshape(-1, 1) * t
+    f[:, 1] = v.reshape(-1, 1)
+    f[:, 3] = l0.reshape(-1, 1)
+    idx = np.full(K * O, int(line_index), dtype=np.int32)
+    cart = native.cartesian_host(f, refline, line_index=idx, want=("cart",))["cart"]
+    pose = np.ascontiguousarray(cart[:, :3].reshape(K, O, 3, int(n)))
+    pose[:, :, 2] += np.broadcast_to(np.asarray(dtheta, dtype=np.float64), (K, O))[:, :, None]
+    half = np.broadcast_to(np.asarray(half, dtype=np.float64), (K, O, 2)).copy()
+    return Obstacles(pose, half, obs_count)
